@@ -5,6 +5,8 @@ box-QP) on MI355X.  Default workload: BASELINE.json configs[1] (cfg2: Duffing, 2
 same JSON shape.
 
     python bench.py --gpus 1 --steps 200 --warmup 20
+    python bench.py --gpus 1 --steps 200 --warmup 20 --full   # the headline and every leg, check and baseline beside it
+    python bench.py --gpus 1 --steps 20 --warmup 5 --dump-outputs DIR    # + what the last timed step computed, as DIR/*.npy
     python bench.py --gpus 8 --steps 200 --warmup 20          # starts its own 8 ranks (torch.distributed.run)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 \
            --master-port 29500 bench.py --gpus 8 --steps 200 --warmup 20
@@ -25,17 +27,26 @@ Rank 0 prints ONE JSON line.  `roofline` is for the dominant kernel: algorithmic
 formula, kmpc_algorithmic_bytes_per_step) x trajectories x steps per launch / its duration measured with
 HIP events on the launch stream in the timed pass itself; `flop_frac` (SURVEY 8d flop formulas with the
 measured Newton-solve count / 78.6 TFLOP/s) beside `hbm_frac`, `bound` = the governing one of the two.
-The default run (cfg2, one GPU) appends `other_configs`: short legs of cfg4, cfg3, cfg3-L20, cfg5, cfg2 at
+
+A plain run does only what the headline needs: set-up, warm-up (with the clock ramp on a scratch controller), the K timed
+steps (measured once more if disturbed, see below), the outputs of --dump-outputs, the line.  Everything below that is not
+the headline -- the CPU baseline, the extra legs, the replicas, the parity probe, the other configurations, the multi-rank
+leg and RCCL's rank count -- runs only with --full.
+
+--dump-outputs DIR writes what the timed path handed its caller after the last timed step (rank 0's trajectories) as
+DIR/<name>.npy: see dump_outputs().  The inputs are seeded, so two builds can be compared file by file.
+
+With --full, the default run (cfg2, one GPU) appends `other_configs`: short legs of cfg4, cfg3, cfg3-L20, cfg5, cfg2 at
 16384 trajectories (a state beyond the Infinity Cache) and cfg2 behind float32 panels (BASELINE configs[1] names fp32)
 with the same K / W, and beside the headline: `replicas` (the timed window five more times: min / median / max of the
 kernel's fraction), `switch_window_*` (K steps from step 95 of a run that starts at the RLS reset: the plant's
 parameter switch of duffing.py:991-992 lies inside), `cold_start_*` (every QP from clip(0) like the reference) and
-`post_reset_*` (the same K steps right after the reset).  With N > 1 ranks the default run appends `roofline.multi_rank.cfg4`: a short leg of the
+`post_reset_*` (the same K steps right after the reset).  With N > 1 ranks the --full run appends `roofline.multi_rank.cfg4`: a short leg of the
 shared-model configuration -- the only one with a collective on its step path -- on all ranks, behind the headline, on a watched thread.
 A headline whose wall time is more than 1.5 x a replica of the same region (a disturbed launch: the pool's devices have them now and then)
 is measured once more from the restored state -- the warm-up and EXACTLY the same K steps --, the shorter figure is the line's and
 `config.headline_retimed` carries the first one.
-`cpu_baseline` times the NumPy oracle run the way the reference runs (per-trajectory Python
+`cpu_baseline` (--full) times the NumPy oracle run the way the reference runs (per-trajectory Python
 loop, SciPy L-BFGS-B on the shooting cost, duffing.py:857-859) on a bounded sample of the same workload IN
 THE SAME REGIME (the settle steps after the reset are set-up, the steps after them are timed): one worker
 process per host core the process may use (affinity mask, capped by the cgroup quota; the count is in the line), forked before
@@ -428,6 +439,51 @@ class Loop:
                 self.m.shared_step(self.X, self.r, plant="tank", switched=(k > 100))
 
 
+DUMP_BYTES_MAX = 64 << 20  # --dump-outputs: at most this much in all
+
+
+def dump_outputs(loop, out_dir, seed=0):
+    """--dump-outputs: what the timed path handed its caller after the last timed step, as out_dir/<name>.npy --
+    `x` the states (n, B), advanced in place; `qp_status` / `newton_solves` each trajectory's worst QP status and Newton solves over
+    the timed launch; `model_A` / `model_B` / `model_C` the model the last step's RLS update left (per trajectory, or the one shared
+    model); the shared-model loop also hands back `u` and `u_sequence`, the last step's inputs and input sequences.  Integer arrays
+    are written as float64, the others in the run's dtype.  Above DUMP_BYTES_MAX in all, a fixed sample of the trajectories (seed
+    `seed`, sorted; `trajectory_index.npy`) stands for the batch.  Returns {name: shape}."""
+    torch = loop.torch
+    m = loop.m
+    arrays = {"x": (loop.X, 1), "qp_status": (m.status, 0), "newton_solves": (m.iters, 0)}  # name -> (tensor, trajectory axis)
+    if loop.shared:
+        A, Bm, Cm = m.shared_model()
+        arrays.update(u=(m.U0, 0), u_sequence=(m.Useq, 1), model_A=(A, None), model_B=(Bm, None), model_C=(Cm, None))
+    else:
+        A, Bm, Cm = m.get_model()
+        arrays.update(model_A=(A, 0), model_B=(Bm, 0), model_C=(Cm, 0))
+    arrays = {k: v for k, v in arrays.items() if v[0] is not None}
+    torch.cuda.synchronize(loop.dev)
+    size = lambda t: t.numel() * (4 if t.dtype == torch.float32 else 8)  # noqa: E731  (int32 is written as float64)
+    total = sum(size(t) for t, _ in arrays.values())
+    idx = None
+    if total > DUMP_BYTES_MAX:
+        per_traj = sum(size(t) for t, ax in arrays.values() if ax is not None) / loop.B
+        fixed = total - per_traj * loop.B
+        k = max(1, min(loop.B, int((DUMP_BYTES_MAX - fixed) // (per_traj + 8))))
+        idx = np.sort(np.random.RandomState(seed).choice(loop.B, k, replace=False))
+    os.makedirs(out_dir, exist_ok=True)
+    shapes = {}
+    for name, (t, ax) in arrays.items():
+        if idx is not None and ax is not None:
+            t = t.index_select(ax, torch.as_tensor(idx, device=t.device))
+        a = t.cpu().numpy()
+        if a.dtype not in (np.float32, np.float64):
+            a = a.astype(np.float64)
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        shapes[name] = a.shape
+    if idx is not None:
+        np.save(os.path.join(out_dir, "trajectory_index.npy"), idx.astype(np.float64))
+        shapes["trajectory_index"] = idx.shape
+    return shapes
+
+
 SWITCH_WINDOW_START = 95  # the `switch_window` leg times K steps from here (the plant switches at step 102, duffing.py:991-992)
 FP64_PEAK_TFLOPS = 78.6  # /opt/skills/guides/MI355X_MICROARCH.md: fp64 vector / matrix peak (spec)
 FP32_PEAK_TFLOPS = 157.3  # fp32 vector peak (spec, packed): the float32 legs
@@ -466,9 +522,10 @@ def executed_flops(name, L, N, q, newton_per_step):
     return lift + rls + rec + hf + qp
 
 
-def measure_config(name, args, dist, dev, rank, world, L, N, B, settle, extras=True, spin_seconds=1.0, probe=True):
+def measure_config(name, args, dist, dev, rank, world, L, N, B, settle, extras=True, spin_seconds=1.0, probe=True, dump=None):
     """Set-up (offline fit, `settle` closed-loop steps), W warm-up steps, then EXACTLY K timed steps of one configuration:
-    returns the fields of the JSON line that depend on the workload (value, ms_per_step, roofline, the QP statistics)."""
+    returns the fields of the JSON line that depend on the workload (value, ms_per_step, roofline, the QP statistics).
+    dump: a directory for what the last timed step computed (dump_outputs, rank 0), written before any leg or probe runs."""
     import torch
     from koopmpc import max_over_ranks
 
@@ -576,6 +633,8 @@ def measure_config(name, args, dist, dev, rank, world, L, N, B, settle, extras=T
                 retimed = dict(first, reason="the first execution of the timed region took more than 1.5 x a replica of it on the scratch controller; the same K steps were run again from the restored state")
             else:
                 retimed = dict(first, reason="a second execution of the region was no shorter: the first figure stands", second_ms_per_step=dt2 / args.steps * 1e3)
+    if dump and rank == 0:
+        dump_outputs(main_loop, dump)
     mpc = main_loop.m
     measure_config.last_plugin = mpc.rollout_plugin_status()
     worst_status = int(mpc.status.max().item())
@@ -811,18 +870,23 @@ def main():
                     help="closed-loop steps after the RLS reset that belong to the set-up (-1: the configuration's default)")
     ap.add_argument("--cold-start", action="store_true",
                     help="start every QP at clip(0) like the reference instead of at the previous minimiser")
-    ap.add_argument("--cpu-seconds", type=float, default=15.0, help="CPU baseline budget (0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the CPU baseline, the cold-start / post-reset / replica / switch-window legs, the parity "
+                         "probe, the other configurations' legs, the multi-rank cfg4 leg and RCCL's rank count (a plain run: the headline only)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step computed (rank 0) as DIR/<name>.npy, float32 / float64, at most 64 MB in all")
+    ap.add_argument("--cpu-seconds", type=float, default=15.0, help="CPU baseline budget with --full (0 = skip)")
     ap.add_argument("--spin-seconds", type=float, default=1.0,
                     help="untimed GPU activity on a scratch copy of the workload before the warm-up, so that the "
                          "clocks have left their idle state when the W warm-up steps start")
     ap.add_argument("--replicas", type=int, default=5, help="replicas of the timed window whose kernel-time spread is reported (roofline.replicas)")
-    ap.add_argument("--no-extras", action="store_true", help="skip the cold-start / post-reset measurements and the other configurations' legs")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the cold-start / post-reset measurements and the other configurations' legs")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="process-group backend for --gpus N > 1: nccl (= RCCL, one GPU per rank) or gloo (rehearsal of the "
                          "multi-rank code path, e.g. with --same-device on a one-GPU box; not a scaling measurement)")
     ap.add_argument("--same-device", action="store_true", help="every rank uses cuda:0 (rehearsal with --backend gloo)")
     ap.add_argument("--probe-worker", default=None, help=argparse.SUPPRESS)  # (child of parity_probe: oracle on the host, no GPU)
-    ap.add_argument("--no-probe", action="store_true", help="skip the parity probe (8 trajectories of the timed state against the oracle)")
+    ap.add_argument("--no-probe", action="store_true", help="with --full: skip the parity probe (8 trajectories of the timed state against the oracle)")
     ap.add_argument("--verbose-line", action="store_true", help="keep the long workload / sample descriptions in the JSON line")
     ap.add_argument("--force-process-group", action="store_true",
                     help="--gpus 1 with a ONE-rank process group of --backend, and the path's collectives executed on it (barrier, MAX, the "
@@ -843,9 +907,10 @@ def main():
     c = CONFIGS[name]
     L, N, B = args.L or c["L"], args.N or c["N"], args.batch or c["B"]
     settle = c["settle"] if args.settle < 0 else args.settle
-    # ---- CPU baseline first (rank 0 at N = 1 only): its worker processes are forked before anything touches the GPU
+    extras = args.full and not args.no_extras
+    # ---- CPU baseline first (--full, rank 0 at N = 1 only): its worker processes are forked before anything touches the GPU
     cpu = None
-    if world == 1 and args.cpu_seconds > 0:
+    if args.full and world == 1 and args.cpu_seconds > 0:
         cpu = cpu_baseline(name, L, N, initial_states_for(name, min(B, 4096), 101), args.cpu_seconds, settle)
     import torch
 
@@ -877,13 +942,13 @@ def main():
         if pg_world != args.gpus:
             sys.exit("bench.py --gpus %d but the process group has %d ranks" % (args.gpus, pg_world))
 
-    res = measure_config(name, args, dist, dev, rank, world, L, N, B, settle, extras=not args.no_extras, spin_seconds=args.spin_seconds,
-                         probe=not args.no_probe)
+    res = measure_config(name, args, dist, dev, rank, world, L, N, B, settle, extras=extras, spin_seconds=args.spin_seconds,
+                         probe=args.full and not args.no_probe, dump=args.dump_outputs)
 
     # ---- the other BASELINE configurations in the same run (short legs, no cold-start / post-reset pair, N = 1 only): what the
     # driver's one line would otherwise not carry
     others = {}
-    if name == "cfg2" and world == 1 and not args.no_extras and not (args.batch or args.L or args.N or args.cold_start):
+    if name == "cfg2" and world == 1 and extras and not (args.batch or args.L or args.N or args.cold_start):
         import copy
 
         def leg(oname, a_, label=None, batch=0):
@@ -951,7 +1016,7 @@ def main():
 
     hung = False
     multi_rank = None
-    if dist is not None and world > 1 and name == "cfg2" and not args.no_extras and not (args.batch or args.L or args.N or args.cold_start):
+    if dist is not None and world > 1 and name == "cfg2" and extras and not (args.batch or args.L or args.N or args.cold_start):
         import copy
 
         oc = CONFIGS["cfg4"]
@@ -971,7 +1036,7 @@ def main():
     # how many ranks RCCL itself reports (ncclCommCount of this process's communicator -- the one the shared-model loop all-reduces
     # on; a per-trajectory configuration creates one here, after the measurement, only to be able to say so): lets SCALE be checked
     rccl_ranks_seen = None
-    if dist is not None and args.backend == "nccl" and not hung:
+    if args.full and dist is not None and args.backend == "nccl" and not hung:
         from koopmpc.sharding import process_communicator
 
         rccl_ranks_seen, err, hung = watched(lambda: process_communicator(dev).count(), 60.0, "ncclCommInitRank / ncclCommCount")

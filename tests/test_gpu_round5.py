@@ -318,7 +318,7 @@ def test_bench_four_ranks_rehearsal(torch_mod, cfg):
     device exported, which only holds if the Gram blocks of all four ranks were summed."""
     N = 4
     d = _bench_child(["--gpus", str(N), "--backend", "gloo", "--same-device", "--config", cfg, "--steps", "4", "--warmup", "2",
-                      "--cpu-seconds", "0", "--spin-seconds", "0", "--no-extras", "--settle", "6", "--batch", "256"])
+                      "--cpu-seconds", "0", "--spin-seconds", "0", "--no-extras", "--settle", "6", "--batch", "256", "--full"])
     assert d["n_gpus"] == N and d["steps"] == 4 and d["warmup"] == 2
     pg = d["config"]["process_group"]
     assert pg["world_size"] == N and pg["backend"] == "gloo" and pg["ranks_share_device"] is True
@@ -336,7 +336,7 @@ def test_bench_one_rank_rccl_reports_ranks_seen(torch_mod):
     (koopmpc.sharding.process_communicator: one per process, destroyed at the end) and the line carries what RCCL itself counts
     (ncclCommCount) as `rccl_ranks_seen` -- 1 here, 8 on the driver's node."""
     d = _bench_child(["--gpus", "1", "--config", "cfg4", "--steps", "4", "--warmup", "2", "--cpu-seconds", "0", "--spin-seconds", "0",
-                      "--no-extras", "--settle", "6", "--batch", "512", "--force-process-group"])
+                      "--no-extras", "--settle", "6", "--batch", "512", "--force-process-group", "--full"])
     pg = d["config"]["process_group"]
     assert pg["world_size"] == 1 and pg["backend"] == "nccl" and pg["rccl_ranks_seen"] == 1
     assert d["config"]["worst_qp_status"] == 0 and d["config"]["finite"] is True

@@ -5,7 +5,7 @@ root=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/../.." && pwd)}
 export KMPC_DEBUG=1 KMPC_FORCE_PLUGIN=1 KMPC_KERNEL_CACHE=/tmp/kmpc_ab_cache KMPC_BENCH_NO_F32_LEG=1
 for r in $(seq 1 $rounds); do
   for f in "$@"; do
-    KMPC_PLUGIN_FLAGS="$f" python3 "$root/bench.py" --config $cfg --cpu-seconds 0 --no-probe --batch 4096 --steps 20 --warmup 5 2>/dev/null | python3 -c "
+    KMPC_PLUGIN_FLAGS="$f" python3 "$root/bench.py" --full --config $cfg --cpu-seconds 0 --no-probe --batch 4096 --steps 20 --warmup 5 2>/dev/null | python3 -c "
 import json,sys
 try:
     d=json.loads([l for l in sys.stdin if l.startswith('{')][-1]); r=d['roofline']
