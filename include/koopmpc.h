@@ -323,8 +323,11 @@ int kmpc_rollout_is_fused(const kmpc_handle* h);
 /* Where that kernel comes from.  The reference's dimensions are constants edited in its scripts (duffing.py:66 Nlift, :632-633
  * MPCHorizon; Koopman_update.m:67, 70, 113: L = 10, N = 10), so the fused roll-out is not tied to a list: libkoopmpc.so holds the
  * instantiations of the BASELINE / reference dimension sets, and kmpc_create makes the kernel of any other set as a PLUG-IN --
- * looked up in the kernel cache ($KMPC_KERNEL_CACHE, <library dir>/kernel_cache, ~/.cache/koopmpc), else compiled from the sources
- * that ship next to the library (csrc/rollout_jit.hip) with hipcc ($KMPC_HIPCC, /opt/rocm/bin/hipcc): 4-8 s, once per set and machine.
+ * looked up in the kernel cache ($KMPC_KERNEL_CACHE, <library dir>/kernel_cache, $XDG_CACHE_HOME/koopmpc, ~/.cache/koopmpc,
+ * $TMPDIR/koopmpc-<uid>), else compiled from the sources that ship next to the library (csrc/rollout_jit.hip) with hipcc
+ * ($KMPC_HIPCC, /opt/rocm/bin/hipcc): 4-8 s, once per set, compiler and machine.  Only directories that are real directories (not
+ * symbolic links), owned by the calling user and not writable by group or others are used, and only objects that are such regular
+ * files are loaded; the text names what was skipped and why.  A launch runs the plug-in the handle loaded: it never compiles.
  * Returns 0: built-in instantiation, 1: plug-in, -1: the plug-in could not be made (the handle works with per-step launches),
  * 2: the configuration has no fused roll-out; `text` (optional, text_bytes long) receives the file / the reason.                */
 int kmpc_rollout_plugin_status(const kmpc_handle* h, char* text, int text_bytes);
@@ -341,7 +344,9 @@ int kmpc_rollout_plugin_prebuild(int n, int L, int N, int out_rows, int lift_kin
 int kmpc_rank_by_work(const int32_t* work_dev, int B, int32_t* perm_dev, void* stream);
 /* Trajectories per workgroup of the fused roll-out kernel (MLP lift): 4, 8 or 16; 0 = automatic (most
  * trajectories per CU, ties to the larger workgroup).  Process-wide tuning / test knob: every
- * trajectory's arithmetic is the same for every choice, only the scheduling differs.
+ * trajectory's arithmetic is the same for every choice, only the scheduling differs.  A handle of a
+ * plug-in dimension set (kmpc_rollout_plugin_status = 1) takes the setting when it is created and
+ * keeps the workgroup of the plug-in it loaded; built-in sets follow it at every launch.
  * Returns -1 for any other value.                                                            */
 int kmpc_set_rollout_workgroup(int trajectories);
 /* algorithmic bytes of one trajectory-step (SURVEY.md 8d formula) for this configuration   */

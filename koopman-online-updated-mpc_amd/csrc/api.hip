@@ -184,7 +184,7 @@ struct Impl : kmpc_handle {
   bool is_core = false;  // this handle IS the float64 core of a float32 handle
   // roll-out plug-in of this handle's dimension set (rollout_plugin.hip): 0 built-in set or no fused roll-out at all, 1 loaded, -1 could not be made
   int plugin_state = 0;
-  RolloutPluginKey plugin_key{};
+  RolloutPlugin plugin{};  // (a launch runs this one: it never looks up or compiles a plug-in)
   std::string plugin_msg;
   // four-wave solver (threads = 256, float64): every trajectory's last tableau and its variable set, kept from step to step
   // (StepArgs::qp_carry); any change of the model from outside forgets them (the next solve starts from 2H)
@@ -255,8 +255,9 @@ struct Impl : kmpc_handle {
       const bool wanted = threads == 64 && n == 2 && !is_core && (c.lift_kind != KMPC_LIFT_MLP || (hid0 >= 1 && hid0 <= 128)) &&
                           (io32 ? (c.output_kind != KMPC_OUT_LIFT && !c.delta_u && rollout_io32_available(n, L, N, q, rbf) && !dbg_env("KMPC_NO_IO32_ROLLOUT"))
                                 : rollout_fused_available<double>(n, L, N, q, threads, rbf));
-      if (wanted && rollout_plugin_key(n, L, N, q, rbf, Lp0, KS0, Hp0, B, io32, &plugin_key)) {
-        plugin_state = rollout_plugin_get(plugin_key, &plugin_msg) ? 1 : -1;
+      if (wanted && rollout_plugin_key(n, L, N, q, rbf, Lp0, KS0, Hp0, B, io32, &plugin.key)) {
+        plugin.fn = rollout_plugin_get(plugin.key, &plugin_msg);
+        plugin_state = plugin.fn ? 1 : -1;
       }
     }
     if constexpr (sizeof(T) == 8) {
@@ -276,6 +277,7 @@ struct Impl : kmpc_handle {
         core->is_core = true;  // (its launches carry float32 panels: this handle's plug-in, loaded above, serves them)
         const int rc = core->init(c64);
         if (rc) { err = "float64 core of the float32 handle: " + core->err; delete core; core = nullptr; return rc; }
+        core->plugin = plugin;
       }
     }
     if (c.lift_kind == KMPC_LIFT_MLP) {
@@ -636,7 +638,7 @@ struct Impl : kmpc_handle {
   long term_count = 0;
   double term_R = 0.01, term_eps = 0.01;
   double *dTermQ = nullptr, *dTermScr = nullptr;
-  RolloutPluginKey term_key{};
+  RolloutPlugin term_plugin{};
   std::string term_msg;
   int set_terminal_refresh(int every, const double* Qh, double R, int maxiter, double eps) override {
     if constexpr (sizeof(T) != 8) {
@@ -666,8 +668,9 @@ struct Impl : kmpc_handle {
       term_plugin_state = 0;
       const bool rbf = cfg.lift_kind != KMPC_LIFT_MLP;
       if (threads == 64 && n == 2 && plugin_state >= 0 && rollout_fused_available<double>(n, L, N, q, threads, rbf) &&
-          rollout_plugin_key(n, L, N, q, rbf, Lp, (hid + 3) / 4, Hp, B, false, &term_key, true)) {
-        term_plugin_state = rollout_plugin_get(term_key, &term_msg) ? 1 : -1;
+          rollout_plugin_key(n, L, N, q, rbf, Lp, (hid + 3) / 4, Hp, B, false, &term_plugin.key, true)) {
+        term_plugin.fn = rollout_plugin_get(term_plugin.key, &term_msg);
+        term_plugin_state = term_plugin.fn ? 1 : -1;
         if (term_plugin_state > 0 && !dTermScr) HIPCHK(hipMalloc(&dTermScr, sizeof(double) * (size_t)B * term_scratch_elems(L)));
       }
       term_every = every;
@@ -1033,9 +1036,9 @@ struct Impl : kmpc_handle {
   // 0: the library's own instantiation, 1: a plug-in (text: its file and whether it was compiled now or found in the kernel cache),
   // -1: the plug-in could not be made (text: why; the handle works with per-step launches), 2: this configuration has no fused roll-out
   int rollout_plugin_status(std::string* text) const override {
-    if (term_every > 0 && term_plugin_state > 0) { if (text) *text = rollout_plugin_describe(term_key); return 1; }
+    if (term_every > 0 && term_plugin_state > 0) { if (text) *text = rollout_plugin_describe(term_plugin.key); return 1; }
     if (term_every > 0 && term_plugin_state < 0) { if (text) *text = term_msg; return -1; }
-    if (plugin_state > 0) { if (text) *text = rollout_plugin_describe(plugin_key); return 1; }
+    if (plugin_state > 0) { if (text) *text = rollout_plugin_describe(plugin.key); return 1; }
     if (plugin_state < 0) { if (text) *text = plugin_msg; return -1; }
     if (!fused_rollout_ok()) { if (text) *text = "no fused roll-out for this configuration (per-step launches)"; return 2; }
     if (text) *text = "built-in instantiation of libkoopmpc.so";
@@ -1121,7 +1124,7 @@ struct Impl : kmpc_handle {
       HIPCHK(hipEventRecord(ev[ev_used], s));
       HIPCHK(hipEventRecord(ev[ev_used + 1], s));  // (no separate lift kernel)
     }
-    HIPCHK(launch_rollout_fused<T>(r, s));
+    HIPCHK(launch_rollout_fused<T>(r, s, term_every > 0 ? &term_plugin : &plugin));
     // (profiling: the closing event sits right behind the roll-out kernel -- until round 5 it sat behind the rank pass below, whose
     //  9 us at B = 4096 were counted into "the dominant kernel's duration": rocprofv3 0.630 ms against 0.647 ms from these events)
     if (rec) {

@@ -196,7 +196,6 @@ size_t step_lds_bytes(int n, int L, int q, int N, size_t elem, int* r1, int* r2,
 template <typename T> hipError_t launch_step(const StepArgs<T>& a, int threads, hipStream_t s);
 // true if (T, n, L, N, q, threads, lift kind) has a fused roll-out instantiation that fits in LDS
 template <typename T> bool rollout_fused_available(int n, int L, int N, int q, int threads, bool rbf);
-template <typename T> hipError_t launch_rollout_fused(const RolloutArgs<T>& a, hipStream_t s);
 void set_rollout_workgroup(int trajectories);  // 0 = automatic, else 4 / 8 / 16 (process-wide)
 // ---- roll-out plug-ins (rollout_plugin.hip, rollout_jit.hip): the fused roll-out of a dimension set without a built-in instantiation
 // nw: trajectories per workgroup; ks: -1 RBF lift, 25 / 0 MLP lift (compile-time / run-time width); term: with the per-step terminal refresh
@@ -204,8 +203,12 @@ struct RolloutPluginKey { int L, N, q, nw, ks, io32, term; };
 typedef hipError_t (*rollout_plugin_fn)(const RolloutArgs<double>* a, int waves, hipStream_t s);
 bool rollout_plugin_dims(int n, int L, int N, int q);  // a plug-in can be generated for this set
 // the loaded plug-in (process table -> kernel cache on disk -> hipcc), or null with *err saying why
-rollout_plugin_fn rollout_plugin_get(const RolloutPluginKey& k, std::string* err, bool build_if_missing = true);
+rollout_plugin_fn rollout_plugin_get(const RolloutPluginKey& k, std::string* err);
 std::string rollout_plugin_describe(const RolloutPluginKey& k);
+struct RolloutPlugin { RolloutPluginKey key{}; rollout_plugin_fn fn = nullptr; };  // what a handle loaded when it was created
+// the fused roll-out; a dimension set without a built-in instantiation (and every TERM launch) runs on `plugin`, at the workgroup size
+// the plug-in was made for -- a launch never looks up or compiles one
+template <typename T> hipError_t launch_rollout_fused(const RolloutArgs<T>& a, hipStream_t s, const RolloutPlugin* plugin);
 bool rollout_builtin(int L, int N, int q, bool io32);  // libkoopmpc.so itself holds the instantiations of this set
 // the plug-in a launch of this configuration needs; false: none (built-in set, or the set does not fit the fused kernel at all)
 // (term: the variant with the per-step terminal refresh -- always a plug-in, also for the built-in sets)

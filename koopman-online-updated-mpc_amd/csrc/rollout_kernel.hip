@@ -841,24 +841,19 @@ bool rollout_plugin_key(int n, int L, int N, int q, bool rbf, int Lp, int KS, in
   out->nw = rbf ? 16 : waves;  // (the RBF kernel never uses the template's tiling: one object serves every workgroup size)
   return true;
 }
-static hipError_t launch_rollout_plugin(const RolloutArgs<double>& a, hipStream_t s) {
-  RolloutPluginKey k{};
-  const bool rbf = a.lift_rbf != 0;
-  if (!rollout_plugin_key(a.s.n, a.s.L, a.s.N, a.s.q, rbf, a.Lp, a.KS, a.Hp, a.s.B, a.io_f32 != 0, &k, a.term_every > 0)) return hipErrorInvalidValue;
-  // (a handle loads its plug-in when it is created; a launch only compiles when the workgroup size was changed afterwards)
-  const rollout_plugin_fn fn = rollout_plugin_get(k, nullptr);
-  if (!fn) return hipErrorInvalidValue;
-  int waves = rollout_waves(a.s.n, a.s.L, a.s.q, a.s.N, rbf, a.Lp, a.s.B);
-  if (a.io_f32 && !rbf && waves == 4) waves = 8;
-  return fn(&a, waves, s);
+static hipError_t launch_rollout_plugin(const RolloutArgs<double>& a, const RolloutPlugin* p, hipStream_t s) {
+  if (!p || !p->fn) return hipErrorInvalidValue;
+  // (the RBF object serves every workgroup size: rollout_waves picks it as for a built-in set)
+  const int waves = p->key.ks < 0 ? rollout_waves(a.s.n, a.s.L, a.s.q, a.s.N, true, a.Lp, a.s.B) : p->key.nw;
+  return p->fn(&a, waves, s);
 }
 // true: the fused roll-out of this dimension set works on the wave image of the state (step_v2.h) instead of the dense blocks
 bool rollout_uses_image(int n, int L, int N, int q) { return n == 2 && step_v2_dims(L, N, q); }
-template <> hipError_t launch_rollout_fused<double>(const RolloutArgs<double>& a, hipStream_t s) {
+template <> hipError_t launch_rollout_fused<double>(const RolloutArgs<double>& a, hipStream_t s, const RolloutPlugin* plugin) {
   if (a.s.B <= 0 || a.steps <= 0) return hipSuccess;
   if (!a.lift_rbf && (a.Hp > 128 || (a.Hp & 15) || a.Lp > 64 || a.KS > 32 || a.nhh < 0 || a.nhh > 2 || a.s.n > 4))
     return hipErrorInvalidValue;
-  if (a.term_every > 0 || !rollout_builtin(a.s.L, a.s.N, a.s.q, a.io_f32 != 0)) return launch_rollout_plugin(a, s);
+  if (a.term_every > 0 || !rollout_builtin(a.s.L, a.s.N, a.s.q, a.io_f32 != 0)) return launch_rollout_plugin(a, plugin, s);
   if (a.io_f32) return launch_rollout_io32(a, s);
   if (a.s.L == 20 && a.s.N == 20 && a.s.q == 2) return launch_rollout_impl<20, 20, 2>(a, s);
   if (a.s.L == 8 && a.s.N == 30 && a.s.q == 2) return launch_rollout_impl<8, 30, 2>(a, s);  // BASELINE cfg3 (RBF lift, y = Cx)
@@ -875,7 +870,7 @@ template <> hipError_t launch_rollout_fused<double>(const RolloutArgs<double>& a
 #endif
   return hipErrorInvalidValue;
 }
-template <> hipError_t launch_rollout_fused<float>(const RolloutArgs<float>&, hipStream_t) { return hipErrorInvalidValue; }
+template <> hipError_t launch_rollout_fused<float>(const RolloutArgs<float>&, hipStream_t, const RolloutPlugin*) { return hipErrorInvalidValue; }
 template bool rollout_fused_available<float>(int, int, int, int, int, bool);
 template bool rollout_fused_available<double>(int, int, int, int, int, bool);
 

@@ -3,12 +3,17 @@
 libkoopmpc.so holds the fused roll-out kernel for the dimension sets BASELINE.json and the reference's scripts use; a controller
 of any other set gets its kernel when it is created (csrc/rollout_plugin.hip: kernel cache on disk, else hipcc on
 csrc/rollout_jit.hip, 4-8 s).  `prebuild` does that step without a device -- `__graft_entry__.build()` calls it for DEFAULT_SETS
-so that the objects travel with the tree."""
+so that the objects travel with the tree, and `prune` then drops the objects of older sources or compilers from the tree's cache."""
 from __future__ import annotations
 
 import ctypes as C
+import os
+import re
 
 from . import _ffi
+
+# rollout_L.._N.._q.._nw.._ks.._f64|f32[_term]_<hash>.so and its lock file; the hash covers the sources, the flags and the compiler
+_OBJECT = re.compile(r"^rollout_\w+_([0-9a-f]{16})\.so(\.lock)?$")
 
 # (n, L, N, out_rows, lift, effective hidden width, batch, dtype)
 #   the MATLAB twin of the reference: liftFun = [x; Encoder(x)] - [0; Encoder(0)], L = 10, N = 10 (Koopman_update.m:67, 70, 113) --
@@ -34,3 +39,21 @@ def prebuild(sets=None, verbose=False):
             print("plug-in %s: %d %s" % (st, code, text))
         out.append((st, code, text))
     return out
+
+
+def object_hash(path):
+    """The hash suffix of a plug-in object's file name, or None."""
+    m = _OBJECT.match(os.path.basename(path))
+    return m.group(1) if m else None
+
+
+def prune(cache_dir, keep_hashes):
+    """Remove the plug-in objects (and their lock files) in `cache_dir` whose hash is not in `keep_hashes`; every other file stays.
+    Returns the names removed."""
+    gone = []
+    for f in sorted(os.listdir(cache_dir)):
+        h = object_hash(f)
+        if h is not None and h not in keep_hashes:
+            os.remove(os.path.join(cache_dir, f))
+            gone.append(f)
+    return gone

@@ -560,6 +560,47 @@ def test_plugin_is_compiled_on_the_box_when_the_cache_is_empty_and_f32_panels_ge
     assert m64b.rollout_plugin_status() == (code, text)
 
 
+def test_plugin_handle_keeps_its_workgroup_and_a_launch_never_compiles(torch_mod, KM, tmp_path, monkeypatch):
+    """A plug-in handle launches the object it loaded when it was created: kmpc_set_rollout_workgroup afterwards neither compiles
+    anything at the launch (the kernel cache is unchanged) nor changes the result -- U and X equal those of a handle run at the default
+    workgroup bit for bit (a trajectory's arithmetic does not depend on its workgroup)."""
+    import re
+
+    torch = torch_mod
+    from koopmpc import _ffi
+    from koopmpc.synth import initial_states, random_mlp_weights
+
+    lib = _ffi.load()
+    monkeypatch.setenv("KMPC_KERNEL_CACHE", str(tmp_path))
+    L, N, B, steps = 12, 9, 40, 7
+    w = random_mlp_weights(2, 100, 3, L, seed=21)
+    rng = np.random.RandomState(5)
+    A, Bm, Cm = rng.randn(L, L) * 0.2 / np.sqrt(L), rng.randn(L, 1) * 0.3, rng.randn(2, L) * 0.3
+    r = np.tile(np.array([[1.0], [0.0]]), (1, N))
+    X0 = initial_states(B, seed=6)
+    m0, m1 = KM(n=2, L=L, N=N, batch=B, weights=w), KM(n=2, L=L, N=N, batch=B, weights=w)
+    code, text = m1.rollout_plugin_status()
+    print(text)
+    assert code == 1 and m1.rollout_is_fused(), text
+    nw = int(re.search(r"_nw(\d+)_", text).group(1))
+    for m in (m0, m1):
+        m.set_model(A, Bm, Cm)
+    X_0, X_1 = _t(torch, X0), _t(torch, X0)
+    U0, Xl0 = m0.rollout("duffing", X_0, r, steps, log=True)
+    torch.cuda.synchronize()
+    listing = sorted(os.listdir(tmp_path))
+    try:
+        assert lib.kmpc_set_rollout_workgroup(8 if nw == 4 else 4) == 0
+        assert m1.rollout_is_fused()
+        U1, Xl1 = m1.rollout("duffing", X_1, r, steps, log=True)
+        torch.cuda.synchronize()
+    finally:
+        lib.kmpc_set_rollout_workgroup(0)
+    assert sorted(os.listdir(tmp_path)) == listing
+    assert int(m0.status.max().item()) == 0 and int(m1.status.max().item()) == 0
+    assert torch.equal(U0, U1) and torch.equal(Xl0, Xl1) and torch.equal(X_0, X_1)
+
+
 # ------------------------------------------------------------------ per-step terminal refresh inside the roll-out
 @pytest.mark.parametrize("L,N,B,lift,lift_offset,every", [(8, 10, 48, "mlp", None, 1), (10, 10, 40, "mlp", "x_psi0", 1), (8, 10, 30, "rbf", None, 1),
                                                           (20, 20, 24, "mlp", None, 3)])

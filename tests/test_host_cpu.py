@@ -4,8 +4,10 @@ sharding + max-over-ranks timing) works over gloo with world_size 2.  No compute
 import ctypes
 import os
 import re
+import shutil
 import subprocess
 import sys
+import time
 
 import numpy as np
 import pytest
@@ -411,6 +413,187 @@ def test_rollout_plugin_requested_by_several_processes_at_once(tmp_path):
     files = os.listdir(tmp_path)
     assert len([f for f in files if f.endswith(".so")]) == 1, files
     assert not [f for f in files if ".tmp." in f or ".log." in f], files
+    # the lock file stays (every process locks the same inode), and a fourth process loads the object without compiling
+    assert len([f for f in files if f.endswith(".so.lock")]) == 1, files
+    [(rc, text)] = _prebuild_in(env, (2, 6, 11, 0, 1, 0, 64, 1))
+    assert rc == 1 and "loaded from the kernel cache" in text, text
+    assert sorted(os.listdir(tmp_path)) == sorted(files)
+
+
+# (the plug-in tests below run the library in fresh processes, from a copy whose own <library dir>/kernel_cache is the test's)
+_RBF, _F64 = 1, 1  # (koopmpc._ffi.KMPC_LIFT_RBF_PY, KMPC_F64)
+_HIPCC = "/opt/rocm/bin/hipcc" if os.access("/opt/rocm/bin/hipcc", os.X_OK) else shutil.which("hipcc")
+
+
+def _plugin_sandbox(root, **env):
+    """libkoopmpc.so and its plug-in sources copied to root/lib, and an environment whose every kernel cache directory lies under root
+    ($HOME, $XDG_CACHE_HOME, $TMPDIR; $KMPC_KERNEL_CACHE and $KMPC_HIPCC only as given): a process started with it is hermetic."""
+    lib = root / "lib"
+    lib.mkdir()
+    shutil.copy(os.path.join(PKG, "libkoopmpc.so"), lib)
+    shutil.copytree(os.path.join(PKG, "csrc"), lib / "csrc", ignore=shutil.ignore_patterns("*.o"))
+    for d in ("home", "tmp"):
+        (root / d).mkdir(mode=0o700)
+    e = {k: v for k, v in os.environ.items() if k not in ("KMPC_KERNEL_CACHE", "KMPC_HIPCC")}
+    e.update(KMPC_LIB=str(lib / "libkoopmpc.so"), HOME=str(root / "home"), XDG_CACHE_HOME=str(root / "home" / "xdg"), TMPDIR=str(root / "tmp"))
+    e.update(env)
+    return e
+
+
+def _hipcc_wrapper(path, version=None, compile_=None):
+    """A compiler for KMPC_HIPCC: `--version` and compiles go to the real hipcc unless replaced by the given shell lines."""
+    path.write_text("#!/bin/sh\nif [ \"$1\" = --version ]; then\n%s\nelse\n%s\nfi\n"
+                    % (version or '%s --version' % _HIPCC, compile_ or '%s "$@"' % _HIPCC))
+    path.chmod(0o755)
+    return str(path)
+
+
+def _prebuild_in(env, *sets):
+    """kmpc_rollout_plugin_prebuild of each set in one fresh process: [(code, text)]."""
+    code = (
+        "import ctypes, sys\n"
+        "sys.path.insert(0, %r)\n"
+        "from koopmpc import _ffi\n"
+        "lib = _ffi.load()\n"
+        "buf = ctypes.create_string_buffer(4096)\n"
+        "for a in %r:\n"
+        "    print(lib.kmpc_rollout_plugin_prebuild(*a, buf, len(buf)), buf.value.decode())\n"
+    ) % (PKG, list(sets))
+    p = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=600)
+    assert p.returncode == 0, p.stderr[-2000:]
+    return [(int(line.split(" ", 1)[0]), line.split(" ", 1)[1]) for line in p.stdout.strip().splitlines()]
+
+
+def test_rollout_plugin_cache_directories_must_be_trusted(tmp_path):
+    """A plug-in is code the process runs: a kernel cache directory that is world-writable, a symbolic link (here to a trusted
+    directory) or owned by another user is skipped -- a valid object under the exact expected name there is not loaded, nothing is
+    written there, and the status text names the directory and why."""
+    S = (2, 5, 9, 0, _RBF, 0, 64, _F64)
+    env = _plugin_sandbox(tmp_path)
+    good = tmp_path / "good"
+    good.mkdir(mode=0o700)
+    [(rc, text)] = _prebuild_in(dict(env, KMPC_KERNEL_CACHE=str(good)), S)
+    assert rc == 1 and "compiled with hipcc" in text and str(good) in text, text
+    [obj] = [f for f in os.listdir(good) if f.endswith(".so")]
+    own = tmp_path / "lib" / "kernel_cache"  # (the trusted place the processes below find the object in)
+    own.mkdir(mode=0o700)
+    shutil.copy(good / obj, own)
+    wide, link, other = tmp_path / "wide", tmp_path / "link", tmp_path / "other"
+    wide.mkdir()
+    shutil.copy(good / obj, wide)
+    wide.chmod(0o777)
+    link.symlink_to(good)
+    cases = [(wide, "writable by group or others"), (link, "a symbolic link")]
+    if os.geteuid() == 0:
+        other.mkdir(mode=0o755)
+        shutil.copy(good / obj, other)
+        os.chown(other, 65534, 65534)
+        cases.append((other, "owned by uid 65534"))
+    else:
+        cases.append(("/usr", "owned by uid %d" % os.stat("/usr").st_uid))
+    for d, why in cases:
+        before = sorted(os.listdir(d))
+        [(rc, text)] = _prebuild_in(dict(env, KMPC_KERNEL_CACHE=str(d)), S)
+        assert rc == 1 and "loaded from the kernel cache" in text and str(own / obj) in text, (d, text)
+        assert "skipped %s: %s" % (d, why) in text, (d, text)
+        assert sorted(os.listdir(d)) == before, d
+
+
+def test_rollout_plugin_cache_directory_modes(tmp_path):
+    """A cache directory the library makes has mode 0700; a pre-existing $TMPDIR/koopmpc-<uid> that fails the trust rule is refused
+    (the compiler here answers --version and fails every compile: no object is needed to see where it would go)."""
+    S = (2, 5, 10, 0, _RBF, 0, 64, _F64)
+    cc = _hipcc_wrapper(tmp_path / "cc", compile_="echo no compiles in this test; exit 1")
+    env = _plugin_sandbox(tmp_path, KMPC_HIPCC=cc)
+    made = tmp_path / "new" / "cache"
+    [(rc, text)] = _prebuild_in(dict(env, KMPC_KERNEL_CACHE=str(made)), S)
+    assert rc == -1 and "no compiles in this test" in text, text
+    assert os.stat(made).st_mode & 0o777 == 0o700
+    assert not [f for f in os.listdir(made) if ".tmp." in f or f.endswith(".so")]
+    # only the temporary directory is left: the library's own cache is world-writable, $HOME and $XDG_CACHE_HOME are unset
+    (tmp_path / "lib" / "kernel_cache").mkdir()
+    (tmp_path / "lib" / "kernel_cache").chmod(0o777)
+    last = tmp_path / "tmp" / ("koopmpc-%d" % os.geteuid())
+    last.mkdir()
+    last.chmod(0o777)
+    env = dict(env, HOME="", XDG_CACHE_HOME="")
+    [(rc, text)] = _prebuild_in(env, S)
+    assert rc == -1 and "no usable kernel cache directory" in text and "skipped %s: writable by group or others" % last in text, text
+    assert os.listdir(last) == []
+    last.rmdir()
+    [(rc, text)] = _prebuild_in(env, S)
+    assert rc == -1 and "no compiles in this test" in text, text
+    assert os.stat(last).st_mode & 0o777 == 0o700
+
+
+def test_rollout_plugin_compile_does_not_block_other_sets(tmp_path):
+    """The process-wide table is not locked across a compile: while one thread waits for hipcc on set X (a compiler that sleeps
+    first), another thread's request for set Y -- already in the kernel cache -- is answered at once."""
+    X, Y = (2, 5, 11, 0, _RBF, 0, 64, _F64), (2, 5, 12, 0, _RBF, 0, 64, _F64)
+    cache = tmp_path / "cache"
+    cache.mkdir(mode=0o700)
+    env = _plugin_sandbox(tmp_path, KMPC_KERNEL_CACHE=str(cache))
+    assert _prebuild_in(env, Y)[0][0] == 1
+    slow = _hipcc_wrapper(tmp_path / "slow_cc", compile_='sleep 4; %s "$@"' % _HIPCC)
+    code = (
+        "import ctypes, os, sys, threading, time\n"
+        "sys.path.insert(0, %r)\n"
+        "from koopmpc import _ffi\n"
+        "lib = _ffi.load()\n"
+        "def pre(a):\n"
+        "    buf = ctypes.create_string_buffer(4096)\n"
+        "    return lib.kmpc_rollout_plugin_prebuild(*a, buf, len(buf)), buf.value.decode()\n"
+        "os.environ['KMPC_HIPCC'] = %r\n"
+        "out = {}\n"
+        "t = threading.Thread(target=lambda: out.update(x=pre(%r)))\n"
+        "t.start()\n"
+        "time.sleep(1.5)\n"
+        "t0 = time.time()\n"
+        "y = pre(%r)\n"
+        "dt, busy = time.time() - t0, t.is_alive()\n"
+        "t.join()\n"
+        "print(repr((y, dt, busy, out['x'])))\n"
+    ) % (PKG, slow, X, Y)
+    p = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=600)
+    assert p.returncode == 0, p.stderr[-2000:]
+    y, dt, busy, x = eval(p.stdout.strip().splitlines()[-1])
+    assert y[0] == 1 and "loaded from the kernel cache" in y[1], y
+    assert busy and dt < 0.5, (dt, busy)
+    assert x[0] == 1 and "compiled with hipcc" in x[1], x
+
+
+def test_rollout_plugin_name_carries_the_compiler(tmp_path):
+    """The object's hash covers the compiler's --version: with the real hipcc two fresh processes agree on the name (the second loads
+    the first one's object); a compiler that says it is another version gets an object of its own."""
+    S = (2, 5, 13, 0, _RBF, 0, 64, _F64)
+    cache = tmp_path / "cache"
+    cache.mkdir(mode=0o700)
+    env = _plugin_sandbox(tmp_path, KMPC_KERNEL_CACHE=str(cache))
+    [(rc1, t1)], [(rc2, t2)] = _prebuild_in(env, S), _prebuild_in(env, S)
+    assert rc1 == 1 and "compiled with hipcc" in t1 and rc2 == 1 and "loaded from the kernel cache" in t2, (t1, t2)
+    [obj] = [f for f in os.listdir(cache) if f.endswith(".so")]
+    assert obj in t1 and obj in t2
+    other = _hipcc_wrapper(tmp_path / "other_cc", version="echo 'HIP version: 0.0.0'; echo 'clang version 0.0.0'")
+    [(rc3, t3)] = _prebuild_in(dict(env, KMPC_HIPCC=other), S)
+    assert rc3 == 1 and "compiled with hipcc" in t3, t3
+    objs = sorted(f for f in os.listdir(cache) if f.endswith(".so"))
+    assert len(objs) == 2 and objs[0][:-20] == objs[1][:-20], objs  # (same set, different _<hash>.so)
+
+
+def test_plugins_prune_keeps_current_objects_and_other_files(tmp_path):
+    """koopmpc.plugins.prune (what __graft_entry__.build() runs on the tree's kernel cache): objects and lock files of other hashes
+    go, those of the current ones and every unrelated file stay."""
+    from koopmpc import plugins
+
+    cur, old = "0123456789abcdef", "fedcba9876543210"
+    names = ["rollout_L10_N10_q2_nw8_ks0_f64_%s.so" % cur, "rollout_L10_N10_q2_nw8_ks0_f64_%s.so.lock" % cur,
+             "rollout_L7_N9_q2_nw16_ksm1_f64_term_%s.so" % cur, "rollout_L10_N10_q2_nw8_ks0_f64_%s.so" % old,
+             "rollout_L10_N10_q2_nw8_ks0_f64_%s.so.lock" % old, "rollout_L7_N9_q2_nw16_ksm1_f32_%s.so" % old, "README", "notes.so"]
+    for n in names:
+        (tmp_path / n).write_text("x")
+    gone = plugins.prune(str(tmp_path), {cur})
+    assert sorted(gone) == sorted(n for n in names if old in n)
+    assert sorted(os.listdir(tmp_path)) == sorted(n for n in names if old not in n)
 
 
 def test_tools_scripts_compile():
