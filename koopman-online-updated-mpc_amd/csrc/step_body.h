@@ -1603,6 +1603,9 @@ __device__ __forceinline__ void step_body(const StepArgs<T>& a, const StepVar<T>
     const T zp = sv.psi_in_regs ? sv.psi_prev_v : sv.psi_prev[il * a.pp_sl + b * a.pp_sb];
     const T yp = sv.psi_in_regs ? sv.psi_now_v : sv.psi_now[il * a.pn_sl + b * a.pn_sb];
     const T xp = a.x_now[(size_t)in * B + b];
+    // (cr[2] holds C, n L_ elements, as 2 per thread.  The step kernels take any n <= 4: a static set with 4 L_ > 2 TPB would lose
+    //  the tail of C at n = 4.  ONE64 is the fused roll-out, which exists for n = 2 alone -- rollout_fused_available.)
+    static_assert((ONE64 ? 2 : 4) * L_ <= 2 * TPB, "one-region RLS block: C (n x L_) must fit the cr[2] prefetch");
     T qr[NQR], cr[2], pr[NPR], kr[NKR];
 #pragma unroll
     for (int i = 0; i < NQR; ++i) { const int e = tid + i * TPB; qr[i] = Qg[e < LL_ ? e : LL_ - 1]; }
@@ -1796,6 +1799,8 @@ __device__ __forceinline__ void step_body(const StepArgs<T>& a, const StepVar<T>
     }
     constexpr int QPRE = (L_ > 0) ? (L_ * L_ + TPB - 1) / TPB : 0;
     constexpr bool PREFETCH = (L_ > 0) && (QPRE <= 17);
+    // (cpre[2] holds C the same way; QPRE <= 17 already implies 4 L_ <= 2 TPB, and the run-time n L <= 2 TPB below guards the use)
+    static_assert(!PREFETCH || 4 * L_ <= 2 * TPB, "general RLS block: C (up to 4 x L_) must fit the cpre[2] prefetch");
     T qpre[PREFETCH ? QPRE : 1], cpre[PREFETCH ? 2 : 1];
     if constexpr (PREFETCH) {
       if (out_cx) {

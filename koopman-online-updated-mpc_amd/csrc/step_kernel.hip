@@ -128,7 +128,9 @@ template <typename T> hipError_t launch_step(const StepArgs<T>& a, int threads, 
     if (a.L == 64 && a.N == 50 && a.q == 2 && a.out_kind == OUT_CX) return launch_impl<T, 256, 64, 50, 2>(a, s);
     return launch_impl<T, 256, 0, 0, 0>(a, s);
   }
-  // (the static instantiations take the output kind from q: y = C x has q <= n <= 4 < 8 <= L rows, y = psi has q = L)
+  // (the static instantiations take the output kind from q -- Q_ == L_ means y = psi --, so they only serve handles where q == L
+  //  says the same as out_kind.  y = C x has q <= n <= 4 rows and may have L <= 4 as well (n = L = q = 4): such a handle runs the
+  //  generic kernel, which reads out_kind.  n is a run-time value in every instantiation: Q_ fixes the rows of C x, not n.)
   if ((a.q == a.L) != (a.out_kind == OUT_LIFT)) return launch_impl<T, 64, 0, 0, 0>(a, s);
   // compile-time specialisations: BASELINE cfg1/cfg2 (L=20, N=20, y = Cx) and the reference's own
   // dimensions (L=8, N=10; y = Cx duffing.py, y = lifted state vanderpol.py)

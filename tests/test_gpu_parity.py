@@ -10,6 +10,7 @@ Tolerances (fp64 path; the reference computes in fp64, duffing.py:48):
   QP            1e-8 absolute on U (|U| <= 6) vs the exact minimiser
   closed loop   1e-6 on u_k vs the oracle controller on the same states (north-star tolerance)
 fp32 path: stated per test (lift 2e-5; the QP/RLS chain cannot meet 1e-6 in fp32).
+State dimensions n = 1, 3, 4 and the row ranges out_row0 / out_rows of C x (q = 3, 4, q < n): tests/test_gpu_state_dims.py, same bounds.
 """
 import os
 
