@@ -356,6 +356,65 @@ int64_t kmpc_algorithmic_bytes_per_step(const kmpc_handle* h);
  * updates so far left it; on = 1 (default) resumes the update with the next transition                               */
 int kmpc_set_online_update(kmpc_handle* h, int on);
 
+/* ---- diagnostics of the closed loop --------------------------------------------------------------------------------------------
+ * Besides logXloc / logUloc the reference's loop records the lifted state it controlled from (logXLOClift, duffing.py:850) and, at
+ * the end of every iteration, the spectral norms of how far the online update moved A, B and C (A_error, B_error, C_error,
+ * duffing.py:985-990); all of them go into DuffingPlotrealtime.mat (duffing.py:1015).  The two entry points below log them INSIDE
+ * the roll-out.  With lambda = 1 an update that continues the estimator's own model changes it by rank one -- [A B] += e g',
+ * e = psi_k - [A B] z, g = P z / (1 + z'P z); C += e_c h', e_c = x_k - C psi_{k-1}, h = bar_Q psi / (1 + psi' bar_Q psi) -- so the
+ * norms are |e| |g[0:L]|, |e| |g[L]| and |e_c| |h| exactly, from values the update holds anyway: no SVD, three numbers per
+ * trajectory-step.
+ *
+ * on = 1 prepares the handle and returns
+ *    0  the diagnostics variant of the fused roll-out kernel is loaded (a plug-in, found in the kernel cache or compiled HERE, never at
+ *       a launch; also for the built-in dimension sets; with a terminal refresh armed, the variant that has both): every
+ *       register-state set, n = 2, y = C x with q <= 2, L <= 30, N <= 32,
+ *    1  this configuration produces the diagnostics through per-step launches (every other set, a handle on per-step launches, a
+ *       plug-in that could not be made: kmpc_last_error says why): a batched kernel in front of each step's update computes the
+ *       same three numbers from the dense state blocks,
+ *   <0  unsupported, with a message: lambda != 1 (K_new = K / lambda + (..) g', Koopman_update.m:270-274: not rank one at any step),
+ *       float32 handles (float64 handles only, as the terminal refresh), a handle that runs the shared-model loop (one Gram-solved
+ *       model is not a rank-one update).
+ * on = 0 releases it.                                                                                                            */
+int kmpc_set_rollout_diagnostics(kmpc_handle* h, int on);
+/* kmpc_rollout with four more optional logs; -3 unless kmpc_set_rollout_diagnostics(h, 1) succeeded.  Apart from them the call gives
+ * what kmpc_rollout gives on the same route -- U_log, X_log, X_dev, status, iters and the handle's state afterwards, bit for bit.
+ *   Psi_log_dev (steps x L x B)   row k: psi(x_k), the lifted state step k controlled from, lift_offset included -- the column
+ *                                 duffing.py:850 appends to logXLOClift
+ *   dA_log_dev, dB_log_dev, dC_log_dev (steps x B)   entry (k, b): the spectral norm of the change that the RLS update executed IN
+ *                                 step k -- the one with the transition (psi_{k-1}, u_{k-1}) -> (psi_k, x_k) -- made to trajectory
+ *                                 b's A, B and C.
+ *       0.0   where step k ran no update: the first step of a handle without a previous transition, kmpc_set_online_update(h, 0);
+ *             dC also for KMPC_OUT_LIFT, where C is not used
+ *       NaN   (quiet, in all three) at a FIRST update after a restart (kmpc_reset / kmpc_state_init; not after kmpc_state_init_from
+ *             or kmpc_offline_fit(init_rls = 1), which continue a consistent model): the estimator starts from K_A = 0, bar_X = 0
+ *             (duffing.py:927-928, 944-945) while the model in use was the offline one, so the change is y g' - A_offline, of full
+ *             rank, and no product of two vector norms.  It happens at most once per estimator start; to get that one entry take
+ *             kmpc_get_model before and after that step (run it as a call of its own) and the 2-norm of the difference, or form it in
+ *             closed form from the restart state (kmpc_estimator_status).
+ * Alignment with the reference: it appends A_error[i] at the END of iteration i, for the update made with the transition of that
+ * iteration; here that update runs at the start of step i + 1.  A_error[i] of the reference is dA_log[i + 1] of a roll-out that
+ * starts at iteration 0 (likewise B, C).                                                                                        */
+int kmpc_rollout_diag(kmpc_handle* h, int plant, void* X_dev, const void* ref_dev, int ref_per_traj, int steps, int step0,
+                      int switch_step, double hstep, void* U_log_dev, void* X_log_dev, void* Psi_log_dev, void* dA_log_dev,
+                      void* dB_log_dev, void* dC_log_dev, int32_t* status_dev, int32_t* iters_dev, void* stream);
+/* The estimator's bookkeeping, read without touching or waiting for anything: bit 0 -- a previous transition (psi_{k-1}, u_{k-1}) exists,
+ * the next step runs an update; bit 1 -- that update would be the FIRST one after a restart (the NaN case of kmpc_rollout_diag: K_A = 0,
+ * bar_X = 0, inv_K_G = P0 I, bar_Q = barQ0 I, duffing.py:927-930, 944-946) and the online update is on.  P0 / barQ0 (optional) receive the
+ * scales of that start.  With them the one entry kmpc_rollout_diag marks NaN is known in closed form: [A B]_new = psi_k g',
+ * g = P0 z / (1 + P0 z'z), C_new = x_k h', h = barQ0 psi / (1 + barQ0 psi'psi) (C_new = 0 with c_skip_first), against the model in use
+ * (kmpc_get_model before the call).  -1 for a null handle.                                                                           */
+int kmpc_estimator_status(const kmpc_handle* h, double* P0, double* barQ0);
+/* Copies of what the next update regresses on: psi(x_{k-1}) ([B][L], trajectory-major) and u_{k-1} ([B]); either may be null.
+ * Stream-ordered and read-only; float64 handles.                                                                                      */
+int kmpc_get_prev_transition(kmpc_handle* h, void* psi_prev_dev, void* u_prev_dev, void* stream);
+/* kmpc_rollout_plugin_prebuild for the diagnostics variant (float64): the plug-in kmpc_set_rollout_diagnostics(h, 1) would load for a
+ * handle of these dimensions, with_term != 0: the variant that also holds the terminal refresh.  Needs no device.  Returns 1: plug-in
+ * (text: its file), 2: this configuration has no fused diagnostics variant (per-step launches), -1: it could not be made, -3: bad
+ * arguments.                                                                                                                     */
+int kmpc_rollout_diag_plugin_prebuild(int n, int L, int N, int out_rows, int lift_kind, int hidden_eff, int batch, int with_term,
+                                      char* text, int text_bytes);
+
 #ifdef __cplusplus
 }
 #endif

@@ -93,6 +93,11 @@ struct kmpc_handle {
   virtual int set_online_update(int on) = 0;
   virtual int rollout(int plant, void* X, const void* ref, int rpt, int steps, int step0, int switch_step, double hs,
                       void* Ulog, void* Xlog, int32_t* st, int32_t* it, hipStream_t s) = 0;
+  virtual int set_rollout_diagnostics(int on) = 0;
+  virtual int estimator_status(double* P0, double* barQ0) const = 0;
+  virtual int get_prev_transition(void* psi_prev, void* u_prev, hipStream_t s) = 0;
+  virtual int rollout_diag(int plant, void* X, const void* ref, int rpt, int steps, int step0, int switch_step, double hs, void* Ulog,
+                           void* Xlog, void* Psilog, void* dAlog, void* dBlog, void* dClog, int32_t* st, int32_t* it, hipStream_t s) = 0;
   virtual int offline_fit(const void* X, const void* Y, const void* U, int M, double ridge, int init_rls, void* A,
                           void* B, void* C, hipStream_t s) = 0;
   virtual int64_t gram_elems() const = 0;
@@ -645,7 +650,11 @@ struct Impl : kmpc_handle {
       FAIL(-2, "kmpc_set_terminal_refresh: float64 handles only (the reference's Riccati iteration is float64)");
     } else {
       if (every < 0 || (every > 0 && (!Qh || maxiter < 1))) FAIL(-3, "kmpc_set_terminal_refresh: bad arguments");
-      if (every == 0) { term_every = 0; return 0; }
+      if (every == 0) {
+        term_every = 0;
+        if (diag_on) (void)load_diag_plugins();  // (diagnostics armed while the refresh was on: now the variant without it)
+        return 0;
+      }
       { int rc = sync_own(); if (rc) return rc; }
       const bool had = have_wterm, had_per_traj = have_wterm && wterm_from_dare && wterm_per_traj;
       const int old_cap = dare_cap;
@@ -674,8 +683,96 @@ struct Impl : kmpc_handle {
         if (term_plugin_state > 0 && !dTermScr) HIPCHK(hipMalloc(&dTermScr, sizeof(double) * (size_t)B * term_scratch_elems(L)));
       }
       term_every = every;
+      if (diag_on) (void)load_diag_plugins();  // (diagnostics armed before the refresh: the variant that has both)
       return 0;
     }
+  }
+
+  // kmpc_set_rollout_diagnostics / kmpc_rollout_diag: the reference's logXLOClift and A_error, B_error, C_error (duffing.py:850, 985-990,
+  // 1015) from inside the roll-out.  Fused route: rollout_kernel<.., DIAG> (a plug-in made by the setter, also for the built-in sets;
+  // with a terminal refresh armed the variant that has both); every other route: rls_diag_kernel in front of each step's update.
+  bool diag_on = false, dg_call = false;
+  int diag_plugin_state = 0, diag_term_plugin_state = 0;  // 0 not asked for, 1 loaded, -1 could not be made / no such variant
+  RolloutPlugin diag_plugin{}, diag_term_plugin{};
+  std::string diag_msg;
+  T* dg_log[4] = {nullptr, nullptr, nullptr, nullptr};  // Psi, dA, dB, dC logs of the kmpc_rollout_diag call that is running
+  // the DIAG variants this handle needs now; 0: the fused route is ready, 1: per-step launches
+  int load_diag_plugins() {
+    if constexpr (sizeof(T) == 8) {
+      const bool rbf = cfg.lift_kind != KMPC_LIFT_MLP;
+      if (!(threads == 64 && n == 2 && use_img && plugin_state >= 0 && rollout_fused_available<double>(n, L, N, q, threads, rbf))) return 1;
+      auto get = [&](bool term, RolloutPlugin* pl, int* state) {
+        if (*state != 0) return;
+        *state = -1;
+        if (!rollout_plugin_key(n, L, N, q, rbf, Lp, (hid + 3) / 4, Hp, B, false, &pl->key, term, true)) { diag_msg = "no diagnostics variant of the fused roll-out for this configuration"; return; }
+        pl->fn = rollout_plugin_get(pl->key, &diag_msg);
+        if (pl->fn) *state = 1;
+      };
+      if (term_every > 0 && term_plugin_state > 0) get(true, &diag_term_plugin, &diag_term_plugin_state);
+      else get(false, &diag_plugin, &diag_plugin_state);
+      return diag_fused_ready() ? 0 : 1;
+    }
+    return 1;
+  }
+  // kmpc_estimator_status: bit 0 a previous transition exists (the next step runs an update), bit 1 that update would be the FIRST one
+  // after a restart (K_A = 0, bar_X = 0, inv_K_G = P0 I, bar_Q = barQ0 I); nothing is touched, nothing is waited for
+  int estimator_status(double* P0o, double* barQ0o) const override {
+    if (P0o) *P0o = cfg.P0;
+    if (barQ0o) *barQ0o = cfg.barQ0;
+    return (have_prev ? 1 : 0) | ((rls_fresh && update_on) ? 2 : 0);
+  }
+  // kmpc_get_prev_transition: copies of psi(x_{k-1}) ([B][L]) and u_{k-1} ([B]) the next update will regress on (stream-ordered, read-only)
+  int get_prev_transition(void* psi_prev, void* u_prev, hipStream_t s) override {
+    if (core) FAIL(-2, "kmpc_get_prev_transition: float64 handles only");
+    if (psi_prev) HIPCHK(hipMemcpyAsync(psi_prev, dPsi[cur ^ 1], sizeof(T) * (size_t)L * B, hipMemcpyDeviceToDevice, s));
+    if (u_prev) HIPCHK(hipMemcpyAsync(u_prev, dUprev, sizeof(T) * (size_t)B, hipMemcpyDeviceToDevice, s));
+    return 0;
+  }
+  bool diag_fused_ready() const { return diag_on && use_img && (term_every > 0 ? diag_term_plugin_state > 0 : diag_plugin_state > 0); }
+  int set_rollout_diagnostics(int on) override {
+    if constexpr (sizeof(T) != 8) {
+      FAIL(-2, "kmpc_set_rollout_diagnostics: float64 handles only (the norms come out of the float64 update)");
+    } else {
+      if (on == 0) { diag_on = false; return 0; }
+      if (cfg.lambda != 1.0) FAIL(-2, "kmpc_set_rollout_diagnostics: needs lambda = 1 -- with a forgetting factor the change of the model is not rank one (Koopman_update.m:270-274)");
+      if (shared_has_samples) FAIL(-2, "kmpc_set_rollout_diagnostics: this handle runs the shared-model loop -- one Gram-solved model is not a rank-one update");
+      diag_on = true;
+      const int route = load_diag_plugins();
+      if (route == 0 && fused_rollout_ok()) return 0;
+      if (route != 0) err = "diagnostics through per-step launches: " + (diag_msg.empty() ? std::string("this configuration has no register-state fused roll-out") : diag_msg);
+      else err = "diagnostics through per-step launches: the handle's roll-out is not fused";
+      return 1;
+    }
+  }
+  int rollout_diag(int plant, void* X, const void* ref, int rpt, int steps, int step0, int switch_step, double hs, void* Ulog, void* Xlog,
+                   void* Psilog, void* dAlog, void* dBlog, void* dClog, int32_t* st, int32_t* it, hipStream_t s) override {
+    if (!diag_on) FAIL(-3, "kmpc_rollout_diag: kmpc_set_rollout_diagnostics(h, 1) has not succeeded on this handle");
+    dg_call = true;
+    dg_log[0] = (T*)Psilog; dg_log[1] = (T*)dAlog; dg_log[2] = (T*)dBlog; dg_log[3] = (T*)dClog;
+    const int rc = rollout(plant, X, ref, rpt, steps, step0, switch_step, hs, Ulog, Xlog, st, it, s);
+    dg_call = false;
+    return rc;
+  }
+  // per-step route: psi(x_k) into the handle's buffer (the step computes the same values again), then the diagnostics of the update the
+  // step is about to make, from the dense blocks as they are before it
+  int diag_before_step(const void* X, int i, hipStream_t s) {
+    if constexpr (sizeof(T) == 8) {
+      int rc = ensure_dense(s, true);
+      if (rc) return rc;
+      if ((rc = lift_to((const T*)X, dPsi[cur], 1, L, B, s))) return rc;
+      RlsDiagArgs d{};
+      d.B = B; d.n = n; d.L = L;
+      d.has_update = (have_prev && update_on) ? 1 : 0; d.first_update = rls_fresh ? 1 : 0; d.use_C = cfg.output_kind == KMPC_OUT_CX ? 1 : 0;
+      d.P = (const double*)dP; d.strideP = sP; d.K = (const double*)dK; d.strideK = sK; d.Qb = (const double*)dQ; d.strideQ = sQ;
+      d.C = (const double*)dC; d.strideC = sC;
+      d.psi_prev = (const double*)dPsi[cur ^ 1]; d.psi_now = (const double*)dPsi[cur]; d.u_prev = (const double*)dUprev; d.x_now = (const double*)X;
+      d.Psi_row = dg_log[0] ? (double*)dg_log[0] + (size_t)i * L * B : nullptr;
+      d.dA_row = dg_log[1] ? (double*)dg_log[1] + (size_t)i * B : nullptr;
+      d.dB_row = dg_log[2] ? (double*)dg_log[2] + (size_t)i * B : nullptr;
+      d.dC_row = dg_log[3] ? (double*)dg_log[3] + (size_t)i * B : nullptr;
+      HIPCHK(launch_rls_diag(d, s));
+    }
+    return 0;
   }
 
   int reset(hipStream_t s) override {
@@ -1036,6 +1133,15 @@ struct Impl : kmpc_handle {
   // 0: the library's own instantiation, 1: a plug-in (text: its file and whether it was compiled now or found in the kernel cache),
   // -1: the plug-in could not be made (text: why; the handle works with per-step launches), 2: this configuration has no fused roll-out
   int rollout_plugin_status(std::string* text) const override {
+    const int code = rollout_plugin_status_plain(text);
+    // (diagnostics armed: kmpc_rollout_diag launches the DIAG object, kmpc_rollout the one above)
+    if (text && diag_on) {
+      if (diag_fused_ready() && fused_rollout_ok()) *text += "; kmpc_rollout_diag: " + rollout_plugin_describe(term_every > 0 ? diag_term_plugin.key : diag_plugin.key);
+      else *text += "; kmpc_rollout_diag: per-step launches" + (diag_msg.empty() ? std::string() : " (" + diag_msg + ")");
+    }
+    return code;
+  }
+  int rollout_plugin_status_plain(std::string* text) const {
     if (term_every > 0 && term_plugin_state > 0) { if (text) *text = rollout_plugin_describe(term_plugin.key); return 1; }
     if (term_every > 0 && term_plugin_state < 0) { if (text) *text = term_msg; return -1; }
     if (plugin_state > 0) { if (text) *text = rollout_plugin_describe(plugin.key); return 1; }
@@ -1085,6 +1191,7 @@ struct Impl : kmpc_handle {
     r.U_log = (T*)Ulog; r.X_log = (T*)Xlog;
     r.io_f32 = io32 ? 1 : 0;
     if (io32 && !r.s.U0) r.s.U0 = dU0;
+    if (dg_call) { r.diag = 1; r.Psi_log = dg_log[0]; r.dA_log = dg_log[1]; r.dB_log = dg_log[2]; r.dC_log = dg_log[3]; }
     if constexpr (sizeof(T) == 8) {
       if (term_every > 0) {
         if (io32) FAIL(-3, "the per-step terminal refresh is a float64 feature");
@@ -1124,7 +1231,7 @@ struct Impl : kmpc_handle {
       HIPCHK(hipEventRecord(ev[ev_used], s));
       HIPCHK(hipEventRecord(ev[ev_used + 1], s));  // (no separate lift kernel)
     }
-    HIPCHK(launch_rollout_fused<T>(r, s, term_every > 0 ? &term_plugin : &plugin));
+    HIPCHK(launch_rollout_fused<T>(r, s, dg_call ? (term_every > 0 ? &diag_term_plugin : &diag_plugin) : (term_every > 0 ? &term_plugin : &plugin)));
     // (profiling: the closing event sits right behind the roll-out kernel -- until round 5 it sat behind the rank pass below, whose
     //  9 us at B = 4096 were counted into "the dominant kernel's duration": rocprofv3 0.630 ms against 0.647 ms from these events)
     if (rec) {
@@ -1165,14 +1272,15 @@ struct Impl : kmpc_handle {
     if (!plant_id_ok(plant)) FAIL(-3, "unknown plant");
     // (the fused roll-out with the MLP lift accumulates status / iterations in LDS and WRITES them when it ends: no zeroing
     //  launches in front of it -- two of the ~70 us a 20-step call spends outside its kernel)
-    const bool kernel_writes_totals = steps > 0 && fused_rollout_ok() && cfg.lift_kind == KMPC_LIFT_MLP;
+    const bool fused = fused_rollout_ok() && (!dg_call || diag_fused_ready());  // (kmpc_rollout_diag: its fused route needs the DIAG plug-in)
+    const bool kernel_writes_totals = steps > 0 && fused && cfg.lift_kind == KMPC_LIFT_MLP;
     if (!kernel_writes_totals) {
       if (st) HIPCHK(hipMemsetAsync(st, 0, sizeof(int32_t) * (size_t)B, s));
       if (it) HIPCHK(hipMemsetAsync(it, 0, sizeof(int32_t) * (size_t)B, s));
     }
-    if (steps > 0 && fused_rollout_ok())
+    if (steps > 0 && fused)
       return rollout_fused(plant, X, ref, rpt, steps, step0, switch_step, hs, Ulog, Xlog, st, it, s);
-    if (steps == 0 && fused_rollout_ok()) {
+    if (steps == 0 && fused) {
       // a call without steps brings the handle into the form the fused roll-out works on (the wave image of a state that was
       // set, restored or stepped through the dense blocks): set-up that the next kmpc_rollout would otherwise pay
       if constexpr (sizeof(T) == 8) {
@@ -1189,6 +1297,7 @@ struct Impl : kmpc_handle {
       T* u = Ulog ? (T*)Ulog + (size_t)i * B : dU0;
       if (n != 2) FAIL(-3, "plants are two-state systems");
       if (!plant_id_ok(plant)) FAIL(-3, "unknown plant");
+      if (dg_call) { const int rcd = diag_before_step(X, i, s); if (rcd) return rcd; }
       accumulate = true;
       fuse_plant = plant; fuse_switched = (switch_step >= 0 && gi >= switch_step) ? 1 : 0; fuse_h = hs;
       int rc = step(X, ref, rpt, u, nullptr, st, it, s);  // lift kernel + fused RLS/condense/QP/plant kernel
@@ -1744,6 +1853,22 @@ int kmpc_rollout_plugin_prebuild(int n, int L, int N, int out_rows, int lift_kin
   say(rollout_plugin_describe(k));
   return 1;
 }
+int kmpc_rollout_diag_plugin_prebuild(int n, int L, int N, int out_rows, int lift_kind, int hidden_eff, int batch, int with_term, char* text, int text_bytes) {
+  auto say = [&](const std::string& t) { if (text && text_bytes > 0) snprintf(text, (size_t)text_bytes, "%s", t.c_str()); };
+  const bool rbf = lift_kind != KMPC_LIFT_MLP;
+  const int q = out_rows > 0 ? out_rows : n;
+  if (n != 2 || L < 1 || N < 1 || batch < 1 || (!rbf && (hidden_eff < 1 || hidden_eff > 128))) { say("bad arguments"); return -3; }
+  const int Hp = hidden_eff <= 112 ? 112 : 128, Lp = ((L + 15) / 16) * 16, KS = (hidden_eff + 3) / 4;
+  RolloutPluginKey k{};
+  if (!rollout_fused_available<double>(n, L, N, q, 64, rbf) || !rollout_plugin_key(n, L, N, q, rbf, Lp, KS, Hp, batch, false, &k, with_term != 0, true)) {
+    say("no fused diagnostics variant for this configuration (per-step launches)");
+    return 2;
+  }
+  std::string err;
+  if (!rollout_plugin_get(k, &err)) { say(err); return -1; }
+  say(rollout_plugin_describe(k));
+  return 1;
+}
 int kmpc_rollout_plugin_status(const kmpc_handle* h, char* text, int text_bytes) {
   if (!h) return -100;
   std::string t;
@@ -1791,6 +1916,14 @@ int kmpc_set_applied_input(kmpc_handle* h, const void* U, int B, void* s) { NNS(
 int kmpc_set_online_update(kmpc_handle* h, int on) { NN(h); return h->set_online_update(on); }
 int kmpc_plant_step(kmpc_handle* h, int plant, void* X, const void* U, double hs, int sw, int B, void* s) { NNS(h, s); return h->plant_step(plant, X, U, hs, sw, B, (hipStream_t)s); }
 int kmpc_rollout(kmpc_handle* h, int plant, void* X, const void* ref, int rpt, int steps, int step0, int sw, double hs, void* Ulog, void* Xlog, int32_t* st, int32_t* it, void* s) { NNS(h, s); return h->rollout(plant, X, ref, rpt, steps, step0, sw, hs, Ulog, Xlog, st, it, (hipStream_t)s); }
+int kmpc_set_rollout_diagnostics(kmpc_handle* h, int on) { NN(h); return h->set_rollout_diagnostics(on); }
+int kmpc_estimator_status(const kmpc_handle* h, double* P0, double* barQ0) { if (!h) return -1; return h->estimator_status(P0, barQ0); }
+int kmpc_get_prev_transition(kmpc_handle* h, void* psi_prev, void* u_prev, void* s) { NNS(h, s); return h->get_prev_transition(psi_prev, u_prev, (hipStream_t)s); }
+int kmpc_rollout_diag(kmpc_handle* h, int plant, void* X, const void* ref, int rpt, int steps, int step0, int sw, double hs, void* Ulog, void* Xlog,
+                      void* Psilog, void* dAlog, void* dBlog, void* dClog, int32_t* st, int32_t* it, void* s) {
+  NNS(h, s);
+  return h->rollout_diag(plant, X, ref, rpt, steps, step0, sw, hs, Ulog, Xlog, Psilog, dAlog, dBlog, dClog, st, it, (hipStream_t)s);
+}
 int kmpc_offline_fit(kmpc_handle* h, const void* X, const void* Y, const void* U, int M, double ridge, int init_rls, void* A, void* B, void* C, void* s) { NNS(h, s); return h->offline_fit(X, Y, U, M, ridge, init_rls, A, B, C, (hipStream_t)s); }
 int64_t kmpc_gram_elems(const kmpc_handle* h) { return h ? h->gram_elems() : -1; }
 // The one collective of the path for native callers: sum of the per-rank Gram blocks over an RCCL communicator.

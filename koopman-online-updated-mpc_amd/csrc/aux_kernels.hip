@@ -241,6 +241,73 @@ hipError_t launch_image_to_state(const double* img, long stride, int n, int L, i
   return hipGetLastError();
 }
 
+// ---- diagnostics of one step's RLS update from the dense state blocks (RlsDiagArgs, kernels.h) ----------------------------------
+// With lam = 1 the update is rank one -- [A B] += e g', C += e_c h' (duffing.py:927-953 in gain form) -- so the spectral norms the
+// reference logs as A_error, B_error, C_error (duffing.py:985-990) are |e| |g[0:L]|, |e| |g[L]| and |e_c| |h|.  One wave per trajectory,
+// launched in front of the step whose update it describes; every matrix is read once, a row at a time across the lanes.
+__device__ __forceinline__ double diag_wave_sum(double v) {
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
+  return v;
+}
+// y_r = sum_j M[r][j] v_j, r < rows, j < cols <= 128 (v_j in lane j & 63, register j >> 6); lane r & 63 keeps y_r in y[r >> 6]
+__device__ __forceinline__ void diag_matvec(const double* M, int rows, int cols, int ld, double v0, double v1, int lane, double (&y)[2]) {
+  y[0] = 0.0; y[1] = 0.0;
+  for (int r = 0; r < rows; ++r) {
+    const double* row = M + (size_t)r * ld;
+    double s = lane < cols ? row[lane] * v0 : 0.0;
+    if (lane + 64 < cols) s += row[lane + 64] * v1;
+    s = diag_wave_sum(s);
+    if ((r & 63) == lane) y[r >> 6] = s;
+  }
+}
+__global__ __launch_bounds__(64) void rls_diag_kernel(const RlsDiagArgs a) {
+  const int b = blockIdx.x, lane = threadIdx.x, L = a.L, p = L + 1, n = a.n, B = a.B;
+  const double* const psn = a.psi_now + (size_t)b * L;
+  if (a.Psi_row && lane < L) a.Psi_row[(size_t)lane * B + b] = psn[lane];
+  double dA = 0.0, dB = 0.0, dC = 0.0;
+  if (a.has_update && a.first_update) {
+    // K_A = 0, bar_X = 0 (duffing.py:927-928, 944-945): the model in use was not the estimator's, the change has full rank
+    dA = dB = dC = __builtin_nan("");
+  } else if (a.has_update) {
+    const double* const psp = a.psi_prev + (size_t)b * L;
+    const double u = a.u_prev[b];
+    const double psi0 = lane < L ? psp[lane] : 0.0;
+    const double z0 = lane < L ? psi0 : (lane == L ? u : 0.0), z1 = lane + 64 == L ? u : 0.0;  // z = [psi; u], p <= 65 elements
+    double pz[2], kz[2];
+    diag_matvec(a.P + (size_t)b * a.strideP, p, p, p, z0, z1, lane, pz);
+    const double d = 1.0 + diag_wave_sum(z0 * pz[0] + z1 * pz[1]);
+    const double g0 = pz[0] / d, g1 = pz[1] / d;
+    diag_matvec(a.K + (size_t)b * a.strideK, L, p, p, z0, z1, lane, kz);
+    const double e = lane < L ? psn[lane] - kz[0] : 0.0;
+    const double en = sqrt(diag_wave_sum(e * e));
+    const double gn = sqrt(diag_wave_sum(lane < L ? g0 * g0 : 0.0));
+    const double gL = L < 64 ? __shfl(g0, L, 64) : __shfl(g1, 0, 64);
+    dA = en * gn;
+    dB = en * fabs(gL);
+    if (a.use_C) {
+      double qp[2], cp[2];
+      diag_matvec(a.Qb + (size_t)b * a.strideQ, L, L, L, psi0, 0.0, lane, qp);
+      const double dc = 1.0 + diag_wave_sum(psi0 * qp[0]);
+      const double h = qp[0] / dc;  // (0 in the lanes beyond L)
+      diag_matvec(a.C + (size_t)b * a.strideC, n, L, L, psi0, 0.0, lane, cp);
+      const double ec = lane < n ? a.x_now[(size_t)lane * B + b] - cp[0] : 0.0;
+      dC = sqrt(diag_wave_sum(ec * ec)) * sqrt(diag_wave_sum(h * h));
+    }
+  }
+  if (lane == 0) {
+    if (a.dA_row) a.dA_row[b] = dA;
+    if (a.dB_row) a.dB_row[b] = dB;
+    if (a.dC_row) a.dC_row[b] = dC;
+  }
+}
+hipError_t launch_rls_diag(const RlsDiagArgs& a, hipStream_t s) {
+  if (a.B <= 0) return hipSuccess;
+  if (a.L < 1 || a.L > 64 || a.n < 1 || a.n > 4) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(rls_diag_kernel, dim3(a.B), dim3(64), 0, s, a);
+  return hipGetLastError();
+}
+
 template <typename S, typename D> __global__ __launch_bounds__(256) void cast_kernel(const S* __restrict__ src, D* __restrict__ dst, size_t count) {
   for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < count; i += (size_t)gridDim.x * 256) dst[i] = (D)src[i];
 }

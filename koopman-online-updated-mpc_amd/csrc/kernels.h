@@ -153,6 +153,15 @@ template <typename T> struct RolloutArgs {
   T* term_scratch;          // [B][term_scratch_stride]: A, X, M, X_next (L*L each), g, w, hu, hv, B (L each), 16 reduction slots
   long term_scratch_stride;
   int32_t* term_iters;      // [B] iterations of the last refresh, or null
+  // Diagnostics of the closed loop (DIAG instantiations of the kernel only -- always plug-ins, kmpc_set_rollout_diagnostics loads them): what
+  // the reference logs besides logXloc / logUloc.  Psi_log (steps x L x B): psi(x_k), the lifted state step k controlled from (logXLOClift,
+  // duffing.py:850).  dA_log, dB_log, dC_log (steps x B): spectral norms of the change the RLS update of step k made to A, B and C
+  // (A_error, B_error, C_error, duffing.py:985-990) -- with lam = 1 the change is rank one, [A B] += e g', C += e_c h', so the norms are
+  // |e| |g[0:L]|, |e| |g[L]|, |e_c| |h| from values the update holds in lanes anyway; 0 where the step ran no update, a quiet NaN at a first
+  // update after a restart (K_A = 0, bar_X = 0: the model in use was not the estimator's, the change has full rank).  Any of the four may be
+  // null.  At the END of the struct: no kernel-argument offset of the instantiations without them moves.
+  int diag;
+  T* Psi_log; T* dA_log; T* dB_log; T* dC_log;
 };
 static constexpr long term_scratch_elems(int L) { return 4L * L * L + 5L * L + 16; }
 // rank every trajectory by its work (descending, ties by index: deterministic) and write the slot -> trajectory table (RolloutArgs::perm)
@@ -192,14 +201,15 @@ hipError_t launch_dare(const DareArgs& a, hipStream_t s);
 size_t step_lds_bytes(int n, int L, int q, int N, size_t elem, int* r1, int* r2, bool lds_tableau = true);
 
 // layout version of StepArgs / RolloutArgs as the roll-out plug-ins see them (rollout_jit.hip): bump with any change of the two structs
-#define KMPC_PLUGIN_ABI 6002
+#define KMPC_PLUGIN_ABI 6003
 template <typename T> hipError_t launch_step(const StepArgs<T>& a, int threads, hipStream_t s);
 // true if (T, n, L, N, q, threads, lift kind) has a fused roll-out instantiation that fits in LDS
 template <typename T> bool rollout_fused_available(int n, int L, int N, int q, int threads, bool rbf);
 void set_rollout_workgroup(int trajectories);  // 0 = automatic, else 4 / 8 / 16 (process-wide)
 // ---- roll-out plug-ins (rollout_plugin.hip, rollout_jit.hip): the fused roll-out of a dimension set without a built-in instantiation
-// nw: trajectories per workgroup; ks: -1 RBF lift, 25 / 0 MLP lift (compile-time / run-time width); term: with the per-step terminal refresh
-struct RolloutPluginKey { int L, N, q, nw, ks, io32, term; };
+// nw: trajectories per workgroup; ks: -1 RBF lift, 25 / 0 MLP lift (compile-time / run-time width); term: with the per-step terminal refresh;
+// diag: with the diagnostics logs (RolloutArgs::diag)
+struct RolloutPluginKey { int L, N, q, nw, ks, io32, term, diag; };
 typedef hipError_t (*rollout_plugin_fn)(const RolloutArgs<double>* a, int waves, hipStream_t s);
 bool rollout_plugin_dims(int n, int L, int N, int q);  // a plug-in can be generated for this set
 // the loaded plug-in (process table -> kernel cache on disk -> hipcc), or null with *err saying why
@@ -211,8 +221,10 @@ struct RolloutPlugin { RolloutPluginKey key{}; rollout_plugin_fn fn = nullptr; }
 template <typename T> hipError_t launch_rollout_fused(const RolloutArgs<T>& a, hipStream_t s, const RolloutPlugin* plugin);
 bool rollout_builtin(int L, int N, int q, bool io32);  // libkoopmpc.so itself holds the instantiations of this set
 // the plug-in a launch of this configuration needs; false: none (built-in set, or the set does not fit the fused kernel at all)
-// (term: the variant with the per-step terminal refresh -- always a plug-in, also for the built-in sets)
-bool rollout_plugin_key(int n, int L, int N, int q, bool rbf, int Lp, int KS, int Hp, int B, bool io32, RolloutPluginKey* out, bool term = false);
+// (term: the variant with the per-step terminal refresh -- always a plug-in, also for the built-in sets; diag: the variant with the
+//  diagnostics logs -- likewise, float64 register-state sets only)
+bool rollout_plugin_key(int n, int L, int N, int q, bool rbf, int Lp, int KS, int Hp, int B, bool io32, RolloutPluginKey* out, bool term = false,
+                        bool diag = false);
 // wave image of one trajectory's state (step_v2.h): [column pair][slot][2] doubles, layer 2 then layer 1
 struct V2Dims {
   int L, n, p, cp, s2, s1;
@@ -231,6 +243,21 @@ hipError_t launch_state_to_image(const double* P, long sP, const double* K, long
                                  int n, int L, int B, double* img, long stride, hipStream_t s);
 hipError_t launch_image_to_state(const double* img, long stride, int n, int L, int B, double* P, long sP, double* K, long sK,
                                  double* Q, long sQ, double* C, long sC, hipStream_t s);
+// Diagnostics of one step's RLS update from the dense state blocks (aux_kernels.hip rls_diag_kernel; the per-step route of
+// kmpc_rollout_diag, and the second implementation the fused DIAG variant is tested against): one wave per trajectory forms z = [psi_prev; u],
+// P z, d = 1 + z'Pz, g = P z / d, e = psi_now - K z and e_c = x_now - C psi_prev, h = bar_Q psi_prev / (1 + psi' bar_Q psi) BEFORE the step's
+// own update runs, and writes |e| |g[0:L]|, |e| |g[L]|, |e_c| |h| (0 without an update, NaN at a first update) and psi_now into the logs' row.
+struct RlsDiagArgs {
+  int B, n, L;
+  int has_update, first_update, use_C;  // use_C = 0: y = psi, no C (dC = 0)
+  const double* P; long strideP; const double* K; long strideK; const double* Qb; long strideQ; const double* C; long strideC;
+  const double* psi_prev; const double* psi_now;  // [B][L]
+  const double* u_prev;                           // [B]
+  const double* x_now;                            // (n x B)
+  double* Psi_row;                                // (L x B) or null
+  double* dA_row; double* dB_row; double* dC_row; // [B] or null
+};
+hipError_t launch_rls_diag(const RlsDiagArgs& a, hipStream_t s);
 template <typename T> hipError_t launch_pack_afrag(const T* src, int Mp, int Hp, int KS, T* dst, hipStream_t s);
 // lift + Gram sums of the transitions in ONE launch (float64, cooperative MLP encoder; round 4), then the fixed-order sum of the partials
 bool lift_gram_available(const LiftArgs<double>& a);

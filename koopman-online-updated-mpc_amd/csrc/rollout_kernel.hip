@@ -227,9 +227,13 @@ __device__ __attribute__((noinline)) void ro_encoder_tiles(const int wv_, const 
 // TERM: with the per-step terminal refresh (RolloutArgs::term_*; Koopman_update.m:215, 381): the step runs in two parts -- RLS, then
 // condensed QP and solve -- with the reference's Riccati iteration on the freshly updated model between them (dare_device.h).  These
 // instantiations are always plug-ins (kmpc_set_terminal_refresh loads them); the kernels without it are what they were.
-template <int L_, int N_, int Q_, int NW, int KS_, typename IOT = double, bool TERM = false>
+// DIAG: with the diagnostics logs (RolloutArgs::diag, Psi_log, dA_log, dB_log, dC_log: the reference's logXLOClift and A_error, B_error,
+// C_error, duffing.py:850, 985-990): the lift's result also goes to Psi_log, the RLS phase of the register-state step stores the norms of
+// the change it makes (step_v2's DIAG).  Float64 register-state sets; always plug-ins too (kmpc_set_rollout_diagnostics loads them).
+template <int L_, int N_, int Q_, int NW, int KS_, typename IOT = double, bool TERM = false, bool DIAG = false>
 __global__ __launch_bounds__((ro_max_threads<L_, N_, Q_, NW, KS_>())) void rollout_kernel(const RolloutArgs<double> ra) {
   static_assert(sizeof(IOT) == 8 || ro_v2<L_, N_, Q_>(), "float32 I/O: register-state dimension sets only");
+  static_assert(!DIAG || (sizeof(IOT) == 8 && ro_v2<L_, N_, Q_>()), "diagnostics: float64 register-state dimension sets only");
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   double* const smem = reinterpret_cast<double*>(smem_raw);
   constexpr int NC = NW == 4 ? 4 : 16;  // trajectory columns of the cooperative encoder
@@ -539,6 +543,14 @@ __global__ __launch_bounds__((ro_max_threads<L_, N_, Q_, NW, KS_>())) void rollo
       double* const wsm = smem + woff;
       double* const psi_now = R.psi[cur];
       if (lane < L) psi_now[(size_t)b * L + lane] = psi_i;  // (state of the handle; the step takes psi from the registers)
+      V2DiagOut dgo{nullptr, nullptr, nullptr};
+      if constexpr (DIAG) {
+        if (R.Psi_log && lane < L) io_st<IOT>(R.Psi_log, ((size_t)k * L + lane) * B + b, psi_i);  // (logXLOClift, duffing.py:850)
+        const size_t kb = (size_t)k * B + b;
+        dgo.dA = R.dA_log ? io_at<IOT>(R.dA_log, kb) : nullptr;
+        dgo.dB = R.dB_log ? io_at<IOT>(R.dB_log, kb) : nullptr;
+        dgo.dC = R.dC_log ? io_at<IOT>(R.dC_log, kb) : nullptr;
+      }
       StepVar<double> sv;
       sv.psi_now = psi_now;
       sv.psi_prev = R.psi[cur ^ 1];
@@ -554,6 +566,13 @@ __global__ __launch_bounds__((ro_max_threads<L_, N_, Q_, NW, KS_>())) void rollo
       // (waves without an encoder tile do the next step's covariance half inside the next lift instead: see above)
       const bool tile_wave = RBF || NW == 4 || wv < ((KS_ > 0 ? (KS_ <= 28 ? 112 : 128) : R.Hp) >> 4) || wv < (R.Lp >> 4);
       sv.cov_ahead = (k + 1 < R.steps && !R.no_update && tile_wave) ? 1 : 0;
+      if constexpr (DIAG) {
+        if (!(sv.phases & PH_RLS) && lane == 0) {  // (no update in this step: the model did not move)
+          if (dgo.dA) io_st<IOT>(dgo.dA, 0, 0.0);
+          if (dgo.dB) io_st<IOT>(dgo.dB, 0, 0.0);
+          if (dgo.dC) io_st<IOT>(dgo.dC, 0, 0.0);
+        }
+      }
       // (16 trajectories per CU with a long horizon -- the RBF roll-out of cfg3 -- : H re-read from LDS, and the active-set
       //  safeguard stays the fall-back on the global-scratch tableau instead of living in registers: 67 -> 51 spilled
       //  registers, 109.7 -> 117.8 M steps/s; its crawling solves are 14 of 327 680 on that workload)
@@ -567,7 +586,7 @@ __global__ __launch_bounds__((ro_max_threads<L_, N_, Q_, NW, KS_>())) void rollo
         sv2.phases = sv.phases & ~PH_RLS;
         double* imgb = V2 ? R.img + (size_t)bk * R.img_stride : nullptr;
         if (sv1.phases) {
-          if constexpr (V2) step_v2<L_, N_, Q_, LOWREG, !LOWREG, IOT, 1>(a, sv1, bk, wsm, imgb);
+          if constexpr (V2) step_v2<L_, N_, Q_, LOWREG, !LOWREG, IOT, 1, DIAG>(a, sv1, bk, wsm, imgb, &dgo);
           else step_body<double, 64, L_, N_, Q_, LOWREG, !LOWREG || Q_ == L_, ro_one_region<L_, N_, Q_, KS_>()>(a, sv1, bk, wsm);
         }
         __threadfence_block();
@@ -597,7 +616,7 @@ __global__ __launch_bounds__((ro_max_threads<L_, N_, Q_, NW, KS_>())) void rollo
         else step_body<double, 64, L_, N_, Q_, LOWREG, !LOWREG || Q_ == L_, ro_one_region<L_, N_, Q_, KS_>()>(a, sv2, bk, wsm);
       } else if constexpr (V2) {
         double* imgb = R.img + (size_t)bk * R.img_stride;
-        step_v2<L_, N_, Q_, LOWREG, !LOWREG, IOT>(a, sv, bk, wsm, imgb);
+        step_v2<L_, N_, Q_, LOWREG, !LOWREG, IOT, 0, DIAG>(a, sv, bk, wsm, imgb, &dgo);
       } else {
         step_body<double, 64, L_, N_, Q_, LOWREG, !LOWREG || Q_ == L_, ro_one_region<L_, N_, Q_, KS_>()>(a, sv, bk, wsm);
       }
@@ -704,18 +723,18 @@ static int rollout_waves(int n, int L, int q, int N, bool rbf, int Lp, int B = 1
     if (rollout_lds_elems(n, L, q, N, true, w, Lp, nullptr) <= cap) return w;
   return 0;
 }
-template <int L_, int N_, int Q_, int NW, int KS_, typename IOT = double, bool TERM = false>
+template <int L_, int N_, int Q_, int NW, int KS_, typename IOT = double, bool TERM = false, bool DIAG = false>
 static hipError_t launch_rollout_nw(const RolloutArgs<double>& k, int waves, size_t lds, hipStream_t s) {
   static size_t configured_dev[16] = {};  // (function attributes are per device)
   size_t& configured = configured_dev[device_slot()];
   if (lds > 64 * 1024 && lds > configured) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&rollout_kernel<L_, N_, Q_, NW, KS_, IOT, TERM>),
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&rollout_kernel<L_, N_, Q_, NW, KS_, IOT, TERM, DIAG>),
                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;
     configured = lds;
   }
   const int grid = (k.s.B + waves - 1) / waves;
-  hipLaunchKernelGGL((rollout_kernel<L_, N_, Q_, NW, KS_, IOT, TERM>), dim3(grid), dim3(64 * waves), lds, s, k);
+  hipLaunchKernelGGL((rollout_kernel<L_, N_, Q_, NW, KS_, IOT, TERM, DIAG>), dim3(grid), dim3(64 * waves), lds, s, k);
   return hipGetLastError();
 }
 
@@ -753,7 +772,8 @@ template <int L_, int N_, int Q_, typename IOT = double> static hipError_t launc
   if ((a.term_every > 0) != (KMPC_JIT_TERM != 0)) return hipErrorInvalidValue;
   if (a.term_every > 0 && (!a.term_Q || !a.term_W || !a.term_scratch || a.term_scratch_stride < term_scratch_elems(L_) || !a.s.Wterm || !a.s.wterm_per_traj))
     return hipErrorInvalidValue;
-  return launch_rollout_nw<L_, N_, Q_, JNW, JKS, IOT, KMPC_JIT_TERM != 0>(k, waves, lds, s);
+  if ((a.diag != 0) != (KMPC_JIT_DIAG != 0)) return hipErrorInvalidValue;
+  return launch_rollout_nw<L_, N_, Q_, JNW, JKS, IOT, KMPC_JIT_TERM != 0, KMPC_JIT_DIAG != 0>(k, waves, lds, s);
 #else
   if (rbf) return launch_rollout_nw<L_, N_, Q_, 16, -1, IOT>(k, waves, lds, s);
   if constexpr (sizeof(IOT) == 4) {  // (float32 I/O: workgroups of sixteen and eight trajectories -- what rollout_waves picks for these sets)
@@ -829,14 +849,15 @@ template <typename T> bool rollout_fused_available(int n, int L, int N, int q, i
   const bool inst = rollout_builtin(L, N, q, false) || rollout_plugin_dims(n, L, N, q);
   return inst && rollout_waves(n, L, q, N, rbf, 64) > 0;  // (Lp <= 64)
 }
-bool rollout_plugin_key(int n, int L, int N, int q, bool rbf, int Lp, int KS, int Hp, int B, bool io32, RolloutPluginKey* out, bool term) {
-  if ((!term && rollout_builtin(L, N, q, io32)) || !rollout_plugin_dims(n, L, N, q)) return false;
+bool rollout_plugin_key(int n, int L, int N, int q, bool rbf, int Lp, int KS, int Hp, int B, bool io32, RolloutPluginKey* out, bool term, bool diag) {
+  if ((!term && !diag && rollout_builtin(L, N, q, io32)) || !rollout_plugin_dims(n, L, N, q)) return false;
   if (term && io32) return false;  // (the refresh is a float64 feature, as kmpc_terminal_from_dare)
+  if (diag && (io32 || !rollout_uses_image(n, L, N, q))) return false;  // (the diagnostics: float64 register-state sets)
   if (io32 && !step_v2_dims(L, N, q)) return false;
   int waves = rollout_waves(n, L, q, N, rbf, Lp, B);
   if (io32 && !rbf && waves == 4) waves = 8;  // (float32 panels: launch_rollout_impl)
   if (waves == 0) return false;
-  out->L = L; out->N = N; out->q = q; out->io32 = io32 ? 1 : 0; out->term = term ? 1 : 0;
+  out->L = L; out->N = N; out->q = q; out->io32 = io32 ? 1 : 0; out->term = term ? 1 : 0; out->diag = diag ? 1 : 0;
   out->ks = rbf ? -1 : ((KS == 25 && Hp == 112) ? 25 : 0);
   out->nw = rbf ? 16 : waves;  // (the RBF kernel never uses the template's tiling: one object serves every workgroup size)
   return true;
@@ -853,7 +874,7 @@ template <> hipError_t launch_rollout_fused<double>(const RolloutArgs<double>& a
   if (a.s.B <= 0 || a.steps <= 0) return hipSuccess;
   if (!a.lift_rbf && (a.Hp > 128 || (a.Hp & 15) || a.Lp > 64 || a.KS > 32 || a.nhh < 0 || a.nhh > 2 || a.s.n > 4))
     return hipErrorInvalidValue;
-  if (a.term_every > 0 || !rollout_builtin(a.s.L, a.s.N, a.s.q, a.io_f32 != 0)) return launch_rollout_plugin(a, plugin, s);
+  if (a.term_every > 0 || a.diag || !rollout_builtin(a.s.L, a.s.N, a.s.q, a.io_f32 != 0)) return launch_rollout_plugin(a, plugin, s);
   if (a.io_f32) return launch_rollout_io32(a, s);
   if (a.s.L == 20 && a.s.N == 20 && a.s.q == 2) return launch_rollout_impl<20, 20, 2>(a, s);
   if (a.s.L == 8 && a.s.N == 30 && a.s.q == 2) return launch_rollout_impl<8, 30, 2>(a, s);  // BASELINE cfg3 (RBF lift, y = Cx)

@@ -5,11 +5,11 @@
 // the reference's scripts use; for any other set the kernel is made when a handle of that set is created (kmpc_create,
 // kmpc_set_terminal_refresh, kmpc_rollout_plugin_prebuild -- never by a launch: the handle keeps what it loaded):
 //
-//   key = (L, N, q, trajectories per workgroup, lift variant, panel type)
+//   key = (L, N, q, trajectories per workgroup, lift variant, panel type, terminal refresh, diagnostics)
 //   1. the process's table of loaded plug-ins (a second thread asking for a key that is being made waits for it; other keys do not),
 //   2. the kernel cache on disk -- $KMPC_KERNEL_CACHE, <library directory>/kernel_cache (what __graft_entry__.build() pre-builds
 //      travels with the tree), $XDG_CACHE_HOME/koopmpc, ~/.cache/koopmpc, $TMPDIR/koopmpc-<uid> -- file
-//      rollout_L.._N.._q.._nw.._ks.._f64|f32_<hash>.so, the hash over the sources, the compiler flags and the compiler's --version, so
+//      rollout_L.._N.._q.._nw.._ks.._f64|f32[_term][_diag]_<hash>.so, the hash over the sources, the compiler flags and the compiler's --version, so
 //      that a changed header or a new ROCm never meets a stale object,
 //   3. hipcc on csrc/rollout_jit.hip (the sources ship next to the library) with the flags of the library's own build, 4-8 s per kernel,
 //      under a file lock (the ranks of a node build an object once; the lock file stays), written under a temporary name and renamed,
@@ -53,8 +53,8 @@ struct Loaded {
 };
 std::mutex g_mu;  // (guards the three tables; never held across a compile)
 std::condition_variable g_cv;
-typedef std::tuple<int, int, int, int, int, int, int> KeyTuple;
-KeyTuple tuple_of(const RolloutPluginKey& k) { return std::make_tuple(k.L, k.N, k.q, k.nw, k.ks, k.io32, k.term); }
+typedef std::tuple<int, int, int, int, int, int, int, int> KeyTuple;
+KeyTuple tuple_of(const RolloutPluginKey& k) { return std::make_tuple(k.L, k.N, k.q, k.nw, k.ks, k.io32, k.term, k.diag); }
 std::map<KeyTuple, Loaded> g_loaded;
 std::map<KeyTuple, std::string> g_failed;  // (a set that failed once is not compiled again and again)
 std::set<KeyTuple> g_making;               // keys a thread of this process is looking up / compiling right now
@@ -199,8 +199,8 @@ std::string object_name(const RolloutPluginKey& k, unsigned long long h) {
   for (const auto& f : extra_flags())
     for (char ch : f) { h ^= (unsigned char)ch; h *= 1099511628211ull; }
   char buf[160];
-  snprintf(buf, sizeof(buf), "rollout_L%d_N%d_q%d_nw%d_ks%s%d_%s%s_%016llx.so", k.L, k.N, k.q, k.nw, k.ks < 0 ? "m" : "", k.ks < 0 ? -k.ks : k.ks,
-           k.io32 ? "f32" : "f64", k.term ? "_term" : "", h);
+  snprintf(buf, sizeof(buf), "rollout_L%d_N%d_q%d_nw%d_ks%s%d_%s%s%s_%016llx.so", k.L, k.N, k.q, k.nw, k.ks < 0 ? "m" : "", k.ks < 0 ? -k.ks : k.ks,
+           k.io32 ? "f32" : "f64", k.term ? "_term" : "", k.diag ? "_diag" : "", h);
   return buf;
 }
 
@@ -268,6 +268,7 @@ bool make_plugin(const RolloutPluginKey& k, Loaded* out, std::string* err) {
     args.push_back("-DKMPC_JIT_KS=" + std::to_string(k.ks));
     args.push_back("-DKMPC_JIT_IO32=" + std::to_string(k.io32 ? 1 : 0));
     args.push_back("-DKMPC_JIT_TERM=" + std::to_string(k.term ? 1 : 0));
+    args.push_back("-DKMPC_JIT_DIAG=" + std::to_string(k.diag ? 1 : 0));
     for (const auto& f : extra_flags()) args.push_back(f);
     for (const std::string& a : {"-I" + src, src + "/rollout_jit.hip", std::string("-o"), tmp}) args.push_back(a);
     std::string log;

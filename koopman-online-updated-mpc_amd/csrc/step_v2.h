@@ -210,8 +210,13 @@ template <int L_> __device__ __forceinline__ int v2_cov_index(int lane) { return
 // PART (the roll-out with the per-step terminal refresh calls the step in two parts with the Riccati iteration between them):
 //   0 the whole step;  1 the RLS phase only (the updated model is in the image when it returns);  2 condensed QP and solve only (the model
 //   comes from the image)
-template <int L_, int N_, int Q_, bool LOWREG, bool ASREG, typename IOT = double, int PART = 0>
-__device__ __forceinline__ void step_v2(const StepArgs<double>& a, const StepVar<double>& sv, const int b, double* const sm, double* const img) {
+// DIAG (the roll-out with the diagnostics logs, RolloutArgs::diag): the RLS phase also forms the spectral norms of the change it makes to
+//   A, B and C -- rank one with lam = 1: |e| |g[0:L]|, |e| |g[L]|, |e_c| |h| -- and lane 0 stores them at dg (null pointers are skipped);
+//   a first update (K_A = 0, bar_X = 0: full rank against the model in use) stores quiet NaNs.  Without it the code is what it was.
+struct V2DiagOut { double* dA; double* dB; double* dC; };
+template <int L_, int N_, int Q_, bool LOWREG, bool ASREG, typename IOT = double, int PART = 0, bool DIAG = false>
+__device__ __forceinline__ void step_v2(const StepArgs<double>& a, const StepVar<double>& sv, const int b, double* const sm, double* const img,
+                                        const V2DiagOut* const dg = nullptr) {
   typedef double d2_t __attribute__((ext_vector_type(2)));
   constexpr int P_ = L_ + 1, CP = (L_ + 2) / 2, NC = 2 * CP, NX = 2, S2 = 2 * L_ + 1, S1 = L_ + NX;
   constexpr int N = N_, q = Q_;
@@ -308,6 +313,25 @@ __device__ __forceinline__ void step_v2(const StepArgs<double>& a, const StepVar
       const double cC = (isC && !(a.c_skip_first && fu)) ? xn - acc1 : 0.0;
       rowupd<P_, NC, -1>(R1, g0, g1, cK);
       rowupd<L_, NC, -1>(R1, h0, h1, cC);
+      if constexpr (DIAG) {
+        // sums of squares over a 32-lane half, two at a time: lanes 0-31 |e|^2 and |g[0:L]|^2, lanes 32-63 |e_c|^2 (the rows of C) and |h|^2.
+        // (the lanes beyond the vectors carry copies of the last row's value -- slot2 / v2_cov_index clamp --: masked)
+        double s1 = half ? cC * cC : cK * cK;
+        double s2 = t < L_ ? (half ? hall * hall : gall * gall) : 0.0;
+        s1 += dpp_shr(s1, 1); s2 += dpp_shr(s2, 1);
+        s1 += dpp_shr(s1, 2); s2 += dpp_shr(s2, 2);
+        s1 += dpp_shr(s1, 4); s2 += dpp_shr(s2, 4);
+        s1 += dpp_shr(s1, 8); s2 += dpp_shr(s2, 8);
+        const double e2 = lane_bcast(s1, 15) + lane_bcast(s1, 31), ec2 = lane_bcast(s1, 47) + lane_bcast(s1, 63);
+        const double g2 = lane_bcast(s2, 15) + lane_bcast(s2, 31), h2 = lane_bcast(s2, 47) + lane_bcast(s2, 63);
+        const double gL = lane_bcast(gall, L_);
+        const double en = __builtin_sqrt(e2), qn = __builtin_nan("");
+        if (tid == 0) {
+          if (dg->dA) io_st<IOT>(dg->dA, 0, fu ? qn : en * __builtin_sqrt(g2));
+          if (dg->dB) io_st<IOT>(dg->dB, 0, fu ? qn : en * __builtin_fabs(gL));
+          if (dg->dC) io_st<IOT>(dg->dC, 0, fu ? qn : __builtin_sqrt(ec2) * __builtin_sqrt(h2));
+        }
+      }
       if (!half && t < S1) {
 #pragma unroll
         for (int c = 0; c < CP; ++c) {

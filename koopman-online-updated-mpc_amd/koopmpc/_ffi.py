@@ -80,6 +80,11 @@ SIGNATURES = {
     "kmpc_set_online_update": (_I, [_VP, _I]),
     "kmpc_plant_step": (_I, [_VP, _I, _VP, _VP, _D, _I, _I, _VP]),
     "kmpc_rollout": (_I, [_VP, _I, _VP, _VP, _I, _I, _I, _I, _D, _VP, _VP, _VP, _VP, _VP]),
+    "kmpc_set_rollout_diagnostics": (_I, [_VP, _I]),
+    "kmpc_estimator_status": (_I, [_VP, _DP, _DP]),
+    "kmpc_get_prev_transition": (_I, [_VP, _VP, _VP, _VP]),
+    "kmpc_rollout_diag": (_I, [_VP, _I, _VP, _VP, _I, _I, _I, _I, _D, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "kmpc_rollout_diag_plugin_prebuild": (_I, [_I, _I, _I, _I, _I, _I, _I, _I, C.c_char_p, _I]),
     "kmpc_state_bytes": (_I64, [_VP]),
     "kmpc_state_export": (_I, [_VP, _VP, _I64]),
     "kmpc_state_import": (_I, [_VP, _VP, _I64]),

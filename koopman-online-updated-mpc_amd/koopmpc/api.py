@@ -498,12 +498,19 @@ class KoopmanMPC:
                                            X.shape[1], self._stream()), "kmpc_plant_step")
         return X
 
-    def rollout(self, kind, X, r, steps, step0=0, switch_step=102, h=0.05, log=False):
+    def rollout(self, kind, X, r, steps, step0=0, switch_step=102, h=0.05, log=False, diagnostics=False):
         """`steps` iterations of the reference loop body (duffing.py:823-1012) enqueued from C++:
         u_i = step(X); X <- plant(X, u_i), switched parameters from iteration `switch_step` on
         (the reference flips them at the end of iteration 101).  X (n,B) device tensor, updated in place.
         self.status / self.iters receive each trajectory's worst QP status and total Newton solves.
-        Returns (U_log (steps,B), X_log (steps,n,B)) when log=True."""
+        Returns (U_log (steps,B), X_log (steps,n,B)) when log=True.
+        diagnostics=True (with log=True): returns (U_log, X_log, diag), diag = {"Psi" (steps,L,B): the lifted state every step
+        controlled from (logXLOClift, duffing.py:850); "dA", "dB", "dC" (steps,B): the spectral norm of the change the online update
+        of step k made to A, B, C (A_error[i] of duffing.py:985-990 is dA[i + 1])}; see rollout_diagnostics."""
+        if diagnostics:
+            if not log:
+                raise ValueError("diagnostics=True returns logs: pass log=True")
+            return self.rollout_diagnostics(kind, X, r, steps, step0=step0, switch_step=switch_step, h=h)
         plant = self._plant_id(kind)
         assert X.is_cuda and X.dtype == self.dtype and X.is_contiguous() and tuple(X.shape) == (self.n, self.B)
         rr, per = self._ref(r)
@@ -515,6 +522,79 @@ class KoopmanMPC:
                                         self._stream()), "kmpc_rollout")
         self._keep = (rr,)  # keep the reference tensor alive until the stream has consumed it
         return (Ul, Xl) if log else None
+
+    def set_rollout_diagnostics(self, on=True):
+        """kmpc_set_rollout_diagnostics: prepare (or release) the handle for rollout(..., diagnostics=True).  Returns 0 when the
+        diagnostics variant of the fused roll-out kernel is loaded, 1 when this configuration produces them through per-step launches;
+        raises for what is unsupported (lam != 1, float32 controllers, the shared-model loop)."""
+        rc = int(self.lib.kmpc_set_rollout_diagnostics(self.h, int(bool(on))))
+        if rc < 0:
+            self._chk(rc, "kmpc_set_rollout_diagnostics")
+        self._diag_route = rc if on else None
+        return rc
+
+    def _rollout_diag_raw(self, plant, X, rr, per, steps, step0, switch_step, h, Ul, Xl, Psi, dA, dB, dC, st, it):
+        self._chk(self.lib.kmpc_rollout_diag(self.h, plant, self._p(X), self._p(rr), per, int(steps), int(step0), int(switch_step), float(h),
+                                             self._p(Ul), self._p(Xl), self._p(Psi), self._p(dA), self._p(dB), self._p(dC),
+                                             self._p(st), self._p(it), self._stream()), "kmpc_rollout_diag")
+
+    def estimator_status(self):
+        """(have_prev, first_update_pending, P0, barQ0) -- kmpc_estimator_status: whether the next step runs an update, whether that
+        update is the first one after a restart, and the scales of the restart state.  Reads flags only."""
+        P0, Q0 = C.c_double(), C.c_double()
+        bits = int(self.lib.kmpc_estimator_status(self.h, C.byref(P0), C.byref(Q0)))
+        if bits < 0:
+            self._chk(bits, "kmpc_estimator_status")
+        return bool(bits & 1), bool(bits & 2), P0.value, Q0.value
+
+    def rollout_diagnostics(self, kind, X, r, steps, step0=0, switch_step=102, h=0.05):
+        """rollout(log=True) with the reference's model-change series: returns (U_log, X_log, diag) as rollout documents.  The steps
+        run as ONE kmpc_rollout_diag call and nothing else touches the controller's state, so controls, states, status and the state
+        afterwards are those of rollout(log=True) on the same route, call after call.
+        No entry is NaN.  kmpc_rollout_diag marks a FIRST update after a restart with NaN: the estimator starts from K_A = 0, bar_X = 0,
+        inv_K_G = P0 I, bar_Q = barQ0 I (duffing.py:927-930, 944-946) while the model in use was the offline one, a change of full rank.
+        Whether such an update falls into this call is known beforehand (estimator_status; it is step 0 of a handle that holds a
+        previous transition, else step 1), and so is its result: [A B] = psi_k g', g = P0 z / (1 + P0 z'z), C = x_k h',
+        h = barQ0 psi / (1 + barQ0 psi'psi).  That one entry is the 2-norm (torch.linalg.matrix_norm, on the device) of this model
+        minus the model in use, which get_model() gives before the call.  Calls without a pending first update -- every call of a
+        running loop -- do nothing but the launch."""
+        if getattr(self, "_diag_route", None) is None:
+            self.set_rollout_diagnostics(True)
+        plant = self._plant_id(kind)
+        assert X.is_cuda and X.dtype == self.dtype and X.is_contiguous() and tuple(X.shape) == (self.n, self.B)
+        rr, per = self._ref(r)
+        steps = int(steps)
+        kw = dict(dtype=self.dtype, device=self.device)
+        Ul, Xl = torch.empty(steps, self.B, **kw), torch.empty(steps, self.n, self.B, **kw)
+        Psi = torch.empty(steps, self.L, self.B, **kw)
+        dA, dB, dC = (torch.empty(steps, self.B, **kw) for _ in range(3))
+        have_prev, pending, P0, Q0 = self.estimator_status()
+        kf = (0 if have_prev else 1) if pending else steps  # the step whose update is the first after a restart
+        if kf < steps:
+            A0, B0, C0 = self.get_model()  # the model in use until that update
+            if have_prev:
+                psi_p, u_p, x_k = torch.empty(self.B, self.L, **kw), torch.empty(self.B, **kw), X.clone()
+                self._chk(self.lib.kmpc_get_prev_transition(self.h, self._p(psi_p), self._p(u_p), self._stream()), "kmpc_get_prev_transition")
+        self._rollout_diag_raw(plant, X, rr, per, steps, step0, switch_step, h, Ul, Xl, Psi, dA, dB, dC, self.status, self.iters)
+        if kf < steps:
+            if not have_prev:
+                psi_p, u_p, x_k = Psi[0].t(), Ul[0], Xl[0]
+            psi_k = Psi[kf].t()                                                # (B, L)
+            z = torch.cat([psi_p, u_p.reshape(self.B, 1)], dim=1)              # (B, L + 1)
+            g = P0 * z / (1.0 + P0 * (z * z).sum(dim=1, keepdim=True))
+            K1 = psi_k.unsqueeze(2) * g.unsqueeze(1)                           # (B, L, L + 1) = psi_k g'
+            dA[kf] = torch.linalg.matrix_norm(K1[:, :, :self.L] - A0, ord=2)
+            dB[kf] = torch.linalg.vector_norm(K1[:, :, self.L] - B0.reshape(self.B, self.L), dim=1)
+            if C0 is not None:
+                hv = Q0 * psi_p / (1.0 + Q0 * (psi_p * psi_p).sum(dim=1, keepdim=True))
+                C1 = x_k.t().unsqueeze(2) * hv.unsqueeze(1)                    # (B, n, L) = x_k h'
+                if self.cfg.c_skip_first:
+                    C1 = torch.zeros_like(C1)                                  # (Tank_System.m:252-254: the first C update only touches bar_Q)
+                dC[kf] = torch.linalg.matrix_norm(C1 - C0, ord=2)
+            else:
+                dC[kf] = 0.0
+        self._keep = (rr,)
+        return Ul, Xl, {"Psi": Psi, "dA": dA, "dB": dB, "dC": dC}
 
     # ------------------------------------------------------------------ checkpoint
     def state_dict(self):

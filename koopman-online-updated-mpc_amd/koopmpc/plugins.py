@@ -12,7 +12,7 @@ import re
 
 from . import _ffi
 
-# rollout_L.._N.._q.._nw.._ks.._f64|f32[_term]_<hash>.so and its lock file; the hash covers the sources, the flags and the compiler
+# rollout_L.._N.._q.._nw.._ks.._f64|f32[_term][_diag]_<hash>.so and its lock file; the hash covers the sources, the flags and the compiler
 _OBJECT = re.compile(r"^rollout_\w+_([0-9a-f]{16})\.so(\.lock)?$")
 
 # (n, L, N, out_rows, lift, effective hidden width, batch, dtype)
@@ -23,15 +23,37 @@ DEFAULT_SETS = [
     (2, 10, 10, 0, "mlp", 104, 4096, "f64"),
     (2, 10, 10, 0, "mlp", 100, 4096, "f64"),
 ]
+# The diagnostics variants of the fused roll-out (kmpc_set_rollout_diagnostics; always plug-ins, float64), in the form of DEFAULT_SETS:
+# the dtype field reads "f64+diag", or "f64+term+diag" for the variant that also holds the terminal refresh.  The reference's set
+# (8, 10), BASELINE cfg2 (20, 20) and cfg3 (8, 30, RBF).
+DIAG_SETS = [
+    (2, 8, 10, 0, "mlp", 100, 64, "f64+diag"),
+    (2, 8, 10, 0, "mlp", 100, 64, "f64+term+diag"),
+    (2, 20, 20, 0, "mlp", 100, 4096, "f64+diag"),
+    (2, 8, 30, 0, "rbf", 0, 4096, "f64+diag"),
+]
+_KIND = {"mlp": _ffi.KMPC_LIFT_MLP, "rbf": _ffi.KMPC_LIFT_RBF_PY, "rbf_matlab": _ffi.KMPC_LIFT_RBF_MATLAB}
 
 
 def prebuild(sets=None, verbose=False):
-    """Make (or find) the plug-ins of the given configurations; returns [(set, code, text)] with code as kmpc_rollout_plugin_status."""
+    """Make (or find) the plug-ins of the given configurations; returns [(set, code, text)] with code as kmpc_rollout_plugin_status
+    (a diagnostics set: 1 plug-in, 2 no fused variant -- per-step launches --, -1 failed).
+    NOTE: without `sets` this is DEFAULT_SETS followed by DIAG_SETS -- four more objects, 5-6 s of hipcc each on a cold cache.
+    `__graft_entry__.build()` calls it this way, so that the diagnostics plug-ins of the reference's and the BASELINE sets travel with
+    the tree and `prune` keeps them."""
     lib = _ffi.load()
     out = []
-    for st in (DEFAULT_SETS if sets is None else sets):
+    for st in ((DEFAULT_SETS + DIAG_SETS) if sets is None else sets):
         n, L, N, out_rows, lift, hidden, batch, dtype = st
-        kind = {"mlp": _ffi.KMPC_LIFT_MLP, "rbf": _ffi.KMPC_LIFT_RBF_PY, "rbf_matlab": _ffi.KMPC_LIFT_RBF_MATLAB}[lift]
+        if dtype.endswith("+diag"):
+            buf = C.create_string_buffer(1024)
+            code = int(lib.kmpc_rollout_diag_plugin_prebuild(n, L, N, out_rows, _KIND[lift], hidden, batch, int("+term" in dtype), buf, len(buf)))
+            text = buf.value.decode("utf-8", "replace")
+            if verbose:
+                print("plug-in %s: %d %s" % (st, code, text))
+            out.append((st, code, text))
+            continue
+        kind = _KIND[lift]
         buf = C.create_string_buffer(1024)
         code = int(lib.kmpc_rollout_plugin_prebuild(n, L, N, out_rows, kind, hidden, batch, _ffi.KMPC_F64 if dtype == "f64" else _ffi.KMPC_F32, buf, len(buf)))
         text = buf.value.decode("utf-8", "replace")

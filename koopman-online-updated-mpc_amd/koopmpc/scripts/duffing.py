@@ -27,6 +27,8 @@ def main():
     ap.add_argument("--model", default=None, help=".npz with A0, B0, C0: the offline model instead of fitting one here")
     ap.add_argument("--out", default=None, help="np.savez the logs here (logXloc, logUloc, like duffing.py:1015)")
     ap.add_argument("--no-update", action="store_true", help="the comparison loop WITHOUT the online update (duffing.py:738-805: logX, logU)")
+    ap.add_argument("--mat", default=None, help="write the reference's result file (DuffingPlotrealtime.mat, duffing.py:1015) for trajectory 0: logXloc, "
+                    "logUloc, logXLOClift, A_error, B_error, C_error, T_EX, tspan -- from one fused roll-out with the diagnostics logs")
     a = ap.parse_args()
 
     if a.weights:
@@ -51,12 +53,21 @@ def main():
     # the loop body duffing.py:847-992, enqueued from C++; plant parameters switch after iteration 101
     if a.no_update:
         mpc.set_online_update(False)
-    logUloc, logXloc = mpc.rollout("duffing", x_loc, r, a.steps, step0=0, switch_step=102, log=True)
+    diag = None
+    if a.mat:
+        logUloc, logXloc, diag = mpc.rollout("duffing", x_loc, r, a.steps, step0=0, switch_step=102, log=True, diagnostics=True)
+    else:
+        logUloc, logXloc = mpc.rollout("duffing", x_loc, r, a.steps, step0=0, switch_step=102, log=True)
     torch.cuda.synchronize()
     print("worst QP status %d, mean Newton solves/step %.2f" % (int(mpc.status.max()), float(mpc.iters.double().mean()) / a.steps))
     print("x_loc[:, 0] after %d steps:" % a.steps, x_loc[:, 0].cpu().numpy(), " u_loc:", float(logUloc[-1, 0]))
     if a.out:
         np.savez(a.out, logXloc=logXloc.cpu().numpy(), logUloc=logUloc.cpu().numpy())
+    if a.mat:
+        from koopmpc.io import save_closed_loop_mat
+
+        save_closed_loop_mat(a.mat, logXloc, logUloc, r=r, traj=0, diagnostics=diag)
+        print("wrote", a.mat)
 
 
 if __name__ == "__main__":
