@@ -161,11 +161,22 @@ struct DevTmp {
   template <typename U> U* as() const { return static_cast<U*>(p); }
 };
 
+// What a caller hands down to the step / solve / roll-out bodies of a handle (nothing of it is kept in the handle).  The default is a plain
+// call: kmpc_step, kmpc_shared_solve, kmpc_rollout.
+struct DiagLogs { void *Psi, *dA, *dB, *dC; };  // the logs of a kmpc_rollout_diag call (RolloutArgs::Psi_log ...), any may be null
+struct StepCtx {
+  bool accumulate = false;         // a step of a roll-out: status / iterations are worst / total over the steps
+  int plant = -1, switched = 0;    // >= 0: the step kernel advances the plant itself, with step h, on X_rw
+  double h = 0.05;
+  void* X_rw = nullptr;
+  const DiagLogs* diag = nullptr;  // the call is a kmpc_rollout_diag
+};
+
 template <typename T>
 struct Impl : kmpc_handle {
   int n, m, L, p, q, N, B, threads;
-  int Hp = 0, Lp = 0;
-  int hid = 0, Lenc = 0;  // effective hidden width / the encoder's own output dimension (lift_offset)
+  EncoderShape enc{};  // the encoder as the kernels see it (effective hidden width, padding, k-steps)
+  int Lenc = 0;        // the encoder's own output dimension (lift_offset)
   std::vector<std::vector<double>> hostW, hostb;  // the layers as given (row-major), kept for finalize_encoder
   long sP, sK, sQ, sC;
   // persistent state
@@ -187,10 +198,28 @@ struct Impl : kmpc_handle {
   // (dense_valid / img_valid as for the wave image) and the other is rebuilt on demand by a cast over the blocks (core_push / core_pull).
   Impl<double>* core = nullptr;
   bool is_core = false;  // this handle IS the float64 core of a float32 handle
-  // roll-out plug-in of this handle's dimension set (rollout_plugin.hip): 0 built-in set or no fused roll-out at all, 1 loaded, -1 could not be made
-  int plugin_state = 0;
-  RolloutPlugin plugin{};  // (a launch runs this one: it never looks up or compiles a plug-in)
-  std::string plugin_msg;
+  // The fused roll-out objects of this handle's dimension set (rollout_plugin.hip), variant[term][diag]: [0][0] the plain kernel (loaded by
+  // init unless the set is built-in), [1][0] with the terminal refresh inside (kmpc_set_terminal_refresh), [.][1] with the diagnostics logs
+  // (kmpc_set_rollout_diagnostics).  state: 0 not asked for / built-in set / no fused roll-out at all, 1 loaded, -1 could not be made or no
+  // such variant.  A launch runs the one variant_of() names: it never looks up or compiles a plug-in.
+  struct RolloutVariant { int state = 0; RolloutPlugin plugin{}; std::string msg; };
+  RolloutVariant variant[2][2];
+  std::string& diag_msg() { return variant[0][1].msg; }  // (the two DIAG variants share one message: whichever load spoke last)
+  const std::string& diag_msg() const { return variant[0][1].msg; }
+  // the variant a call runs now: with the refresh armed the TERM objects, a kmpc_rollout_diag call the DIAG ones
+  const RolloutVariant& variant_of(bool diag_call) const { return variant[term_every > 0][diag_call]; }
+  // asks for the object of variant[term][diag] (process table, kernel cache, else hipcc); false: this configuration has no such object
+  bool load_variant(bool term, bool diag) {
+    RolloutVariant& v = variant[term][diag];
+    if (!rollout_plugin_key(n, L, N, q, cfg.lift_kind != KMPC_LIFT_MLP, enc.Lp, enc.KS, enc.Hp, B, sizeof(T) == 4, &v.plugin.key, term, diag)) return false;
+    v.plugin.fn = rollout_plugin_get(v.plugin.key, diag ? &diag_msg() : &v.msg);
+    v.state = v.plugin.fn ? 1 : -1;
+    return true;
+  }
+  // this handle's dimension set can run fused at all (single-wave trajectories, two states, an instantiation or a plug-in that was not refused)
+  bool fused_dims_ok() const {
+    return threads == 64 && n == 2 && variant[0][0].state >= 0 && rollout_fused_available<double>(n, L, N, q, threads, cfg.lift_kind != KMPC_LIFT_MLP);
+  }
   // four-wave solver (threads = 256, float64): every trajectory's last tableau and its variable set, kept from step to step
   // (StepArgs::qp_carry); any change of the model from outside forgets them (the next solve starts from 2H)
   T* dQpCarry = nullptr;
@@ -253,36 +282,28 @@ struct Impl : kmpc_handle {
     }
     // a dimension set without a built-in fused roll-out gets its kernel now (rollout_plugin.hip: kernel cache, else hipcc, 4-8 s);
     // a set that cannot be served stays on per-step launches and kmpc_rollout_plugin_status says why
-    {
-      const bool rbf = c.lift_kind != KMPC_LIFT_MLP;
-      const int hid0 = c.hidden + (c.lift_offset == 2 ? 2 * n : 0), Hp0 = hid0 <= 112 ? 112 : 128, Lp0 = ((L + 15) / 16) * 16, KS0 = (hid0 + 3) / 4;
-      const bool io32 = sizeof(T) == 4;
-      const bool wanted = threads == 64 && n == 2 && !is_core && (c.lift_kind != KMPC_LIFT_MLP || (hid0 >= 1 && hid0 <= 128)) &&
-                          (io32 ? (c.output_kind != KMPC_OUT_LIFT && !c.delta_u && rollout_io32_available(n, L, N, q, rbf) && !dbg_env("KMPC_NO_IO32_ROLLOUT"))
-                                : rollout_fused_available<double>(n, L, N, q, threads, rbf));
-      if (wanted && rollout_plugin_key(n, L, N, q, rbf, Lp0, KS0, Hp0, B, io32, &plugin.key)) {
-        plugin.fn = rollout_plugin_get(plugin.key, &plugin_msg);
-        plugin_state = plugin.fn ? 1 : -1;
-      }
-    }
+    enc = encoder_shape(c.hidden, c.lift_offset, n, L);
+    // a float32 handle runs the float64 fused roll-out behind float32 panels (its core, below)
+    // (KMPC_NO_IO32_ROLLOUT is a measurement / test aid: float32 handles as per-step launches)
+    const bool io32_ok = sizeof(T) == 4 && c.output_kind != KMPC_OUT_LIFT && !c.delta_u && rollout_io32_available(n, L, N, q, c.lift_kind != KMPC_LIFT_MLP) &&
+                         !dbg_env("KMPC_NO_IO32_ROLLOUT");
+    if (fused_dims_ok() && !is_core && (c.lift_kind != KMPC_LIFT_MLP || (enc.hid >= 1 && enc.hid <= 128)) && (sizeof(T) == 8 || io32_ok)) load_variant(false, false);
     if constexpr (sizeof(T) == 8) {
-      use_img = threads == 64 && plugin_state >= 0 && (c.output_kind != KMPC_OUT_LIFT || q == L) && rollout_uses_image(n, L, N, q) &&
-                rollout_fused_available<T>(n, L, N, q, threads, c.lift_kind != KMPC_LIFT_MLP);
+      use_img = fused_dims_ok() && (c.output_kind != KMPC_OUT_LIFT || q == L) && rollout_uses_image(n, L, N, q);
       if (use_img) {
         sImg = state_image_elems(L, n);
         HIPCHK(hipMalloc(&dImg, sizeof(double) * (size_t)sImg * B));
       }
     }
     if constexpr (sizeof(T) == 4) {
-      if (threads == 64 && plugin_state >= 0 && c.output_kind != KMPC_OUT_LIFT && !c.delta_u && rollout_io32_available(n, L, N, q, c.lift_kind != KMPC_LIFT_MLP) &&
-          !dbg_env("KMPC_NO_IO32_ROLLOUT")) {  // (the variable is a measurement / test aid: float32 handles as per-step launches)
+      if (fused_dims_ok() && io32_ok) {
         kmpc_config c64 = c;
         c64.dtype = KMPC_F64;
         core = new Impl<double>();
         core->is_core = true;  // (its launches carry float32 panels: this handle's plug-in, loaded above, serves them)
         const int rc = core->init(c64);
         if (rc) { err = "float64 core of the float32 handle: " + core->err; delete core; core = nullptr; return rc; }
-        core->plugin = plugin;
+        core->variant[0][0].plugin = variant[0][0].plugin;
       }
     }
     if (c.lift_kind == KMPC_LIFT_MLP) {
@@ -293,12 +314,10 @@ struct Impl : kmpc_handle {
       // relu(x), relu(-x) through the layers with identity weights and the first n output rows read x = relu(x) - relu(-x)
       // back (exact: one of the two is zero).  Either way the kernels see an ordinary encoder (finalize_encoder).
       if (c.lift_offset < 0 || c.lift_offset > 2) FAIL(-2, "lift_offset must be 0, 1 or 2");
-      hid = c.hidden + (c.lift_offset == 2 ? 2 * n : 0);
       Lenc = L - (c.lift_offset == 2 ? n : 0);
       if (Lenc < 1) FAIL(-2, "lift_offset = 2 needs L > n (L = n + the encoder's output dimension)");
-      if (hid > 128) FAIL(-2, "hidden + 2 n must not exceed 128 with lift_offset = 2");
-      Hp = hid <= 112 ? 112 : 128;
-      Lp = ((L + 15) / 16) * 16;
+      if (enc.hid > 128) FAIL(-2, "hidden + 2 n must not exceed 128 with lift_offset = 2");
+      const int Hp = enc.Hp, Lp = enc.Lp;
       HIPCHK(hipMalloc(&dW1, sizeof(T) * Hp * 4));
       HIPCHK(hipMalloc(&db1, sizeof(T) * Hp));
       for (int k = 0; k < c.layers - 1; ++k) {
@@ -461,7 +480,7 @@ struct Impl : kmpc_handle {
     for (int k = 0; k < nl; ++k) {
       const bool first = k == 0, last = k == nl - 1;
       const int rin = first ? n : H, rout = last ? Lenc : H;          // the given layer
-      const int ein = first ? n : hid, eout = last ? L : hid;         // the effective one
+      const int ein = first ? n : enc.hid, eout = last ? L : enc.hid; // the effective one
       std::vector<double> We((size_t)eout * ein, 0.0), be((size_t)eout, 0.0);
       const int r0 = (last && off == 2) ? n : 0;                       // (the first n output rows are x)
       for (int r = 0; r < rout; ++r) {
@@ -478,14 +497,14 @@ struct Impl : kmpc_handle {
         }
       }
       if (first) {
-        if ((rc = upload_padded(dW1, We.data(), eout, ein, Hp, 4))) return rc;
-        if ((rc = upload_padded(db1, be.data(), 1, eout, 1, Hp))) return rc;
+        if ((rc = upload_padded(dW1, We.data(), eout, ein, enc.Hp, 4))) return rc;
+        if ((rc = upload_padded(db1, be.data(), 1, eout, 1, enc.Hp))) return rc;
       } else if (last) {
-        if ((rc = upload_padded(dWo, We.data(), eout, ein, Lp, Hp))) return rc;
-        if ((rc = upload_padded(dbo, be.data(), 1, eout, 1, Lp))) return rc;
+        if ((rc = upload_padded(dWo, We.data(), eout, ein, enc.Lp, enc.Hp))) return rc;
+        if ((rc = upload_padded(dbo, be.data(), 1, eout, 1, enc.Lp))) return rc;
       } else {
-        if ((rc = upload_padded(dWh[k - 1], We.data(), eout, ein, Hp, Hp))) return rc;
-        if ((rc = upload_padded(dbh[k - 1], be.data(), 1, eout, 1, Hp))) return rc;
+        if ((rc = upload_padded(dWh[k - 1], We.data(), eout, ein, enc.Hp, enc.Hp))) return rc;
+        if ((rc = upload_padded(dbh[k - 1], be.data(), 1, eout, 1, enc.Hp))) return rc;
       }
     }
     packed_ok = false;
@@ -639,12 +658,10 @@ struct Impl : kmpc_handle {
   // (duffing.py:583-598) on every trajectory's freshly updated [A B] each `every`-th step and rebuild its block Co P Co' before the
   // condensed QP is formed -- INSIDE the launch for the fused roll-out (rollout_kernel<.., TERM>, a plug-in made here), as RLS launch /
   // dare_kernel / QP launch on the per-step route.  0: off (the blocks stay what the last refresh left).
-  int term_every = 0, term_maxiter = 500, term_plugin_state = 0;
+  int term_every = 0, term_maxiter = 500;
   long term_count = 0;
   double term_R = 0.01, term_eps = 0.01;
   double *dTermQ = nullptr, *dTermScr = nullptr;
-  RolloutPlugin term_plugin{};
-  std::string term_msg;
   int set_terminal_refresh(int every, const double* Qh, double R, int maxiter, double eps) override {
     if constexpr (sizeof(T) != 8) {
       FAIL(-2, "kmpc_set_terminal_refresh: float64 handles only (the reference's Riccati iteration is float64)");
@@ -674,14 +691,9 @@ struct Impl : kmpc_handle {
       have_wterm = true; wterm_from_dare = true; wterm_per_traj = true;
       term_R = R; term_maxiter = maxiter; term_eps = eps; term_count = 0;
       // the fused roll-out of this configuration with the refresh inside: a plug-in of its own (also for the built-in dimension sets)
-      term_plugin_state = 0;
-      const bool rbf = cfg.lift_kind != KMPC_LIFT_MLP;
-      if (threads == 64 && n == 2 && plugin_state >= 0 && rollout_fused_available<double>(n, L, N, q, threads, rbf) &&
-          rollout_plugin_key(n, L, N, q, rbf, Lp, (hid + 3) / 4, Hp, B, false, &term_plugin.key, true)) {
-        term_plugin.fn = rollout_plugin_get(term_plugin.key, &term_msg);
-        term_plugin_state = term_plugin.fn ? 1 : -1;
-        if (term_plugin_state > 0 && !dTermScr) HIPCHK(hipMalloc(&dTermScr, sizeof(double) * (size_t)B * term_scratch_elems(L)));
-      }
+      variant[1][0].state = 0;
+      if (fused_dims_ok()) load_variant(true, false);
+      if (variant[1][0].state > 0 && !dTermScr) HIPCHK(hipMalloc(&dTermScr, sizeof(double) * (size_t)B * term_scratch_elems(L)));
       term_every = every;
       if (diag_on) (void)load_diag_plugins();  // (diagnostics armed before the refresh: the variant that has both)
       return 0;
@@ -691,25 +703,16 @@ struct Impl : kmpc_handle {
   // kmpc_set_rollout_diagnostics / kmpc_rollout_diag: the reference's logXLOClift and A_error, B_error, C_error (duffing.py:850, 985-990,
   // 1015) from inside the roll-out.  Fused route: rollout_kernel<.., DIAG> (a plug-in made by the setter, also for the built-in sets;
   // with a terminal refresh armed the variant that has both); every other route: rls_diag_kernel in front of each step's update.
-  bool diag_on = false, dg_call = false;
-  int diag_plugin_state = 0, diag_term_plugin_state = 0;  // 0 not asked for, 1 loaded, -1 could not be made / no such variant
-  RolloutPlugin diag_plugin{}, diag_term_plugin{};
-  std::string diag_msg;
-  T* dg_log[4] = {nullptr, nullptr, nullptr, nullptr};  // Psi, dA, dB, dC logs of the kmpc_rollout_diag call that is running
-  // the DIAG variants this handle needs now; 0: the fused route is ready, 1: per-step launches
+  bool diag_on = false;
+  // the DIAG variant this handle needs now (asked for once); 0: the fused route is ready, 1: per-step launches
   int load_diag_plugins() {
     if constexpr (sizeof(T) == 8) {
-      const bool rbf = cfg.lift_kind != KMPC_LIFT_MLP;
-      if (!(threads == 64 && n == 2 && use_img && plugin_state >= 0 && rollout_fused_available<double>(n, L, N, q, threads, rbf))) return 1;
-      auto get = [&](bool term, RolloutPlugin* pl, int* state) {
-        if (*state != 0) return;
-        *state = -1;
-        if (!rollout_plugin_key(n, L, N, q, rbf, Lp, (hid + 3) / 4, Hp, B, false, &pl->key, term, true)) { diag_msg = "no diagnostics variant of the fused roll-out for this configuration"; return; }
-        pl->fn = rollout_plugin_get(pl->key, &diag_msg);
-        if (pl->fn) *state = 1;
-      };
-      if (term_every > 0 && term_plugin_state > 0) get(true, &diag_term_plugin, &diag_term_plugin_state);
-      else get(false, &diag_plugin, &diag_plugin_state);
+      if (!(fused_dims_ok() && use_img)) return 1;
+      const bool term = term_every > 0 && variant[1][0].state > 0;
+      if (variant[term][1].state == 0 && !load_variant(term, true)) {
+        variant[term][1].state = -1;
+        diag_msg() = "no diagnostics variant of the fused roll-out for this configuration";
+      }
       return diag_fused_ready() ? 0 : 1;
     }
     return 1;
@@ -728,7 +731,7 @@ struct Impl : kmpc_handle {
     if (u_prev) HIPCHK(hipMemcpyAsync(u_prev, dUprev, sizeof(T) * (size_t)B, hipMemcpyDeviceToDevice, s));
     return 0;
   }
-  bool diag_fused_ready() const { return diag_on && use_img && (term_every > 0 ? diag_term_plugin_state > 0 : diag_plugin_state > 0); }
+  bool diag_fused_ready() const { return diag_on && use_img && variant_of(true).state > 0; }
   int set_rollout_diagnostics(int on) override {
     if constexpr (sizeof(T) != 8) {
       FAIL(-2, "kmpc_set_rollout_diagnostics: float64 handles only (the norms come out of the float64 update)");
@@ -739,7 +742,7 @@ struct Impl : kmpc_handle {
       diag_on = true;
       const int route = load_diag_plugins();
       if (route == 0 && fused_rollout_ok()) return 0;
-      if (route != 0) err = "diagnostics through per-step launches: " + (diag_msg.empty() ? std::string("this configuration has no register-state fused roll-out") : diag_msg);
+      if (route != 0) err = "diagnostics through per-step launches: " + (diag_msg().empty() ? std::string("this configuration has no register-state fused roll-out") : diag_msg());
       else err = "diagnostics through per-step launches: the handle's roll-out is not fused";
       return 1;
     }
@@ -747,15 +750,14 @@ struct Impl : kmpc_handle {
   int rollout_diag(int plant, void* X, const void* ref, int rpt, int steps, int step0, int switch_step, double hs, void* Ulog, void* Xlog,
                    void* Psilog, void* dAlog, void* dBlog, void* dClog, int32_t* st, int32_t* it, hipStream_t s) override {
     if (!diag_on) FAIL(-3, "kmpc_rollout_diag: kmpc_set_rollout_diagnostics(h, 1) has not succeeded on this handle");
-    dg_call = true;
-    dg_log[0] = (T*)Psilog; dg_log[1] = (T*)dAlog; dg_log[2] = (T*)dBlog; dg_log[3] = (T*)dClog;
-    const int rc = rollout(plant, X, ref, rpt, steps, step0, switch_step, hs, Ulog, Xlog, st, it, s);
-    dg_call = false;
-    return rc;
+    const DiagLogs logs{Psilog, dAlog, dBlog, dClog};
+    StepCtx ctx;
+    ctx.diag = &logs;
+    return rollout_impl(ctx, plant, X, ref, rpt, steps, step0, switch_step, hs, Ulog, Xlog, st, it, s);
   }
   // per-step route: psi(x_k) into the handle's buffer (the step computes the same values again), then the diagnostics of the update the
   // step is about to make, from the dense blocks as they are before it
-  int diag_before_step(const void* X, int i, hipStream_t s) {
+  int diag_before_step(const DiagLogs& lg, const void* X, int i, hipStream_t s) {
     if constexpr (sizeof(T) == 8) {
       int rc = ensure_dense(s, true);
       if (rc) return rc;
@@ -766,10 +768,10 @@ struct Impl : kmpc_handle {
       d.P = (const double*)dP; d.strideP = sP; d.K = (const double*)dK; d.strideK = sK; d.Qb = (const double*)dQ; d.strideQ = sQ;
       d.C = (const double*)dC; d.strideC = sC;
       d.psi_prev = (const double*)dPsi[cur ^ 1]; d.psi_now = (const double*)dPsi[cur]; d.u_prev = (const double*)dUprev; d.x_now = (const double*)X;
-      d.Psi_row = dg_log[0] ? (double*)dg_log[0] + (size_t)i * L * B : nullptr;
-      d.dA_row = dg_log[1] ? (double*)dg_log[1] + (size_t)i * B : nullptr;
-      d.dB_row = dg_log[2] ? (double*)dg_log[2] + (size_t)i * B : nullptr;
-      d.dC_row = dg_log[3] ? (double*)dg_log[3] + (size_t)i * B : nullptr;
+      d.Psi_row = lg.Psi ? (double*)lg.Psi + (size_t)i * L * B : nullptr;
+      d.dA_row = lg.dA ? (double*)lg.dA + (size_t)i * B : nullptr;
+      d.dB_row = lg.dB ? (double*)lg.dB + (size_t)i * B : nullptr;
+      d.dC_row = lg.dC ? (double*)lg.dC + (size_t)i * B : nullptr;
       HIPCHK(launch_rls_diag(d, s));
     }
     return 0;
@@ -851,13 +853,13 @@ struct Impl : kmpc_handle {
     int rc = check_lift_ready();
     if (rc) return rc;
     LiftArgs<T> a{};
-    a.B = Bc; a.n = n; a.L = L; a.hidden = hid; a.nlayers = cfg.layers;
+    a.B = Bc; a.n = n; a.L = L; a.hidden = enc.hid; a.nlayers = cfg.layers;
     a.X = X; a.Psi = Psi; a.ps_l = ps_l; a.ps_b = ps_b;
     if (cfg.lift_kind == KMPC_LIFT_MLP) {
       a.W1 = dW1; a.b1 = db1; a.Wh[0] = dWh[0]; a.Wh[1] = dWh[1]; a.bh[0] = dbh[0]; a.bh[1] = dbh[1];
-      a.Wo = dWo; a.bo = dbo; a.Hp = Hp; a.Lp = Lp;
+      a.Wo = dWo; a.bo = dbo; a.Hp = enc.Hp; a.Lp = enc.Lp;
       if ((rc = pack_encoder(s))) return rc;
-      a.Whp[0] = dWhp[0]; a.Whp[1] = dWhp[1] ? dWhp[1] : dWhp[0]; a.Wop = dWop; a.KSp = (hid + 3) / 4;
+      a.Whp[0] = dWhp[0]; a.Whp[1] = dWhp[1] ? dWhp[1] : dWhp[0]; a.Wop = dWop; a.KSp = enc.KS;
       HIPCHK(launch_lift_mlp<T>(a, s));
     } else {
       a.cx = dcx; a.eps = (T)cfg.rbf_eps; a.rbf_matlab = cfg.lift_kind == KMPC_LIFT_RBF_MATLAB;
@@ -1018,34 +1020,50 @@ struct Impl : kmpc_handle {
     return 0;
   }
 
-  int step(const void* X, const void* ref, int rpt, void* U0, void* Useq, int32_t* st, int32_t* it,
-           hipStream_t s) override {
+  // profiling: one event triple per recorded launch sequence -- its begin, behind its lift (at once where the kernel lifts itself), its end
+  int prof_begin(hipStream_t s, bool* rec) {
+    *rec = prof && ev_used + 3 <= EV_CAP;
+    if (!*rec) return 0;
+    while (ev.size() < ev_used + 3) {
+      hipEvent_t e;
+      HIPCHK(hipEventCreate(&e));
+      ev.push_back(e);
+    }
+    HIPCHK(hipEventRecord(ev[ev_used], s));
+    return 0;
+  }
+  int prof_mid(hipStream_t s) {
+    HIPCHK(hipEventRecord(ev[ev_used + 1], s));
+    return 0;
+  }
+  int prof_end(hipStream_t s, int steps) {
+    HIPCHK(hipEventRecord(ev[ev_used + 2], s));
+    ev_used += 3;
+    prof_steps += steps;
+    return 0;
+  }
+
+  int step(const void* X, const void* ref, int rpt, void* U0, void* Useq, int32_t* st, int32_t* it, hipStream_t s) override {
+    return step_impl(StepCtx{}, X, ref, rpt, U0, Useq, st, it, s);
+  }
+  int step_impl(const StepCtx& ctx, const void* X, const void* ref, int rpt, void* U0, void* Useq, int32_t* st, int32_t* it, hipStream_t s) {
     if (!X || !ref || !U0) FAIL(-3, "kmpc_step: null pointer");
     // Configurations with a fused roll-out instantiation and the MLP lift take ONE launch for the step as well: the
     // roll-out kernel with a single step and no plant (encoder inside on MFMA, no separate lift kernel, psi handed
     // over in registers).  Same results up to the summation order of the encoder.
-    if (sizeof(T) == 8 && fuse_plant < 0 && !accumulate && cfg.lift_kind == KMPC_LIFT_MLP && fused_rollout_ok()) {
+    if (sizeof(T) == 8 && ctx.plant < 0 && !ctx.accumulate && cfg.lift_kind == KMPC_LIFT_MLP && fused_rollout_ok()) {
       static const bool two = dbg_env("KMPC_STEP_TWO_KERNELS") != nullptr;  // measurement aid
       if (!two)
-        return rollout_fused(-1, const_cast<void*>(X), ref, rpt, 1, 0, -1, 0.05, nullptr, nullptr, st, it, s, U0, Useq);
+        return rollout_fused(ctx, -1, const_cast<void*>(X), ref, rpt, 1, 0, -1, 0.05, nullptr, nullptr, st, it, s, U0, Useq);
     }
-    hipEvent_t e0 = nullptr, e1 = nullptr, e2 = nullptr;
-    const bool rec = prof && ev_used + 3 <= EV_CAP;
-    if (rec) {
-      while (ev.size() < ev_used + 3) {
-        hipEvent_t e;
-        HIPCHK(hipEventCreate(&e));
-        ev.push_back(e);
-      }
-      e0 = ev[ev_used]; e1 = ev[ev_used + 1]; e2 = ev[ev_used + 2];
-      HIPCHK(hipEventRecord(e0, s));
-    }
-    int rc = ensure_dense(s, true);  // (first: on a float32 handle the ping-pong index follows the core's)
+    bool rec;
+    int rc = prof_begin(s, &rec);
     if (rc) return rc;
+    if ((rc = ensure_dense(s, true))) return rc;  // (first: on a float32 handle the ping-pong index follows the core's)
     T* psi_now = dPsi[cur];
     T* psi_prev = dPsi[cur ^ 1];
     if ((rc = lift_to((const T*)X, psi_now, 1, L, B, s))) return rc;
-    if (rec) HIPCHK(hipEventRecord(e1, s));
+    if (rec && (rc = prof_mid(s))) return rc;
     StepArgs<T> a = base_args(B);
     a.phases = PH_CONDENSE | PH_QP | ((have_prev && update_on) ? PH_RLS : 0);
     a.first_update = rls_fresh ? 1 : 0;
@@ -1056,8 +1074,8 @@ struct Impl : kmpc_handle {
     a.U0 = (T*)U0; a.Useq = (T*)Useq; a.u_store = dUprev; a.status = st; a.iters = it;
     a.x_warm = cfg.cold_start ? nullptr : dWarm;
     a.qp_carry = dQpCarry; a.qp_carry_set = dQpCarrySet;
-    a.accumulate = accumulate ? 1 : 0;
-    if (fuse_plant >= 0) { a.plant = fuse_plant; a.plant_switched = fuse_switched; a.plant_h = (T)fuse_h; a.X_rw = (T*)const_cast<void*>(X); }
+    a.accumulate = ctx.accumulate ? 1 : 0;
+    if (ctx.plant >= 0) { a.plant = ctx.plant; a.plant_switched = ctx.switched; a.plant_h = (T)ctx.h; a.X_rw = (T*)ctx.X_rw; }
     if (term_every > 0) {
       // per-step terminal refresh on the per-step route: the RLS update as a launch of its own, the Riccati iteration on the updated
       // models (dare_kernel, every term_every-th step), then condensed QP and solve with the refreshed blocks
@@ -1073,11 +1091,7 @@ struct Impl : kmpc_handle {
       term_count += 1;
     }
     HIPCHK(launch_step<T>(a, threads, s));
-    if (rec) {
-      HIPCHK(hipEventRecord(e2, s));
-      ev_used += 3;
-      prof_steps += 1;
-    }
+    if (rec && (rc = prof_end(s, 1))) return rc;
     if (have_prev && update_on) rls_fresh = false;
     have_prev = true;
     cur ^= 1;
@@ -1112,14 +1126,14 @@ struct Impl : kmpc_handle {
   int64_t prof_steps = 0;   // profiling: control steps covered by the recorded events
   int pack_encoder(hipStream_t s) {
     if (packed_ok) return 0;
-    const int KS = (hid + 3) / 4;
+    const int KS = enc.KS;
     const int nhh = cfg.layers - 1;
     for (int k = 0; k < nhh; ++k) {
-      if (!dWhp[k]) HIPCHK(hipMalloc(&dWhp[k], sizeof(T) * (size_t)(Hp / 16) * KS * 64));
-      HIPCHK(launch_pack_afrag<T>(dWh[k], Hp, Hp, KS, dWhp[k], s));
+      if (!dWhp[k]) HIPCHK(hipMalloc(&dWhp[k], sizeof(T) * (size_t)(enc.Hp / 16) * KS * 64));
+      HIPCHK(launch_pack_afrag<T>(dWh[k], enc.Hp, enc.Hp, KS, dWhp[k], s));
     }
-    if (!dWop) HIPCHK(hipMalloc(&dWop, sizeof(T) * (size_t)(Lp / 16) * KS * 64));
-    HIPCHK(launch_pack_afrag<T>(dWo, Lp, Hp, KS, dWop, s));
+    if (!dWop) HIPCHK(hipMalloc(&dWop, sizeof(T) * (size_t)(enc.Lp / 16) * KS * 64));
+    HIPCHK(launch_pack_afrag<T>(dWo, enc.Lp, enc.Hp, KS, dWop, s));
     packed_ok = true;
     return 0;
   }
@@ -1127,8 +1141,8 @@ struct Impl : kmpc_handle {
   bool fused_rollout_ok() const {
     static const bool off = dbg_env("KMPC_NO_FUSED_ROLLOUT") != nullptr;  // measurement aid: per-step launches
     if (core) return !off && core->fused_rollout_ok();  // (float32 panels around the float64 roll-out)
-    if (term_every > 0 && term_plugin_state <= 0) return false;  // (the refresh needs the TERM plug-in; else the per-step route)
-    return !off && n == 2 && plugin_state >= 0 && rollout_fused_available<T>(n, L, N, q, threads, cfg.lift_kind != KMPC_LIFT_MLP);
+    if (term_every > 0 && variant_of(false).state <= 0) return false;  // (the refresh needs the TERM plug-in; else the per-step route)
+    return !off && sizeof(T) == 8 && fused_dims_ok();
   }
   // 0: the library's own instantiation, 1: a plug-in (text: its file and whether it was compiled now or found in the kernel cache),
   // -1: the plug-in could not be made (text: why; the handle works with per-step launches), 2: this configuration has no fused roll-out
@@ -1136,22 +1150,22 @@ struct Impl : kmpc_handle {
     const int code = rollout_plugin_status_plain(text);
     // (diagnostics armed: kmpc_rollout_diag launches the DIAG object, kmpc_rollout the one above)
     if (text && diag_on) {
-      if (diag_fused_ready() && fused_rollout_ok()) *text += "; kmpc_rollout_diag: " + rollout_plugin_describe(term_every > 0 ? diag_term_plugin.key : diag_plugin.key);
-      else *text += "; kmpc_rollout_diag: per-step launches" + (diag_msg.empty() ? std::string() : " (" + diag_msg + ")");
+      if (diag_fused_ready() && fused_rollout_ok()) *text += "; kmpc_rollout_diag: " + rollout_plugin_describe(variant_of(true).plugin.key);
+      else *text += "; kmpc_rollout_diag: per-step launches" + (diag_msg().empty() ? std::string() : " (" + diag_msg() + ")");
     }
     return code;
   }
   int rollout_plugin_status_plain(std::string* text) const {
-    if (term_every > 0 && term_plugin_state > 0) { if (text) *text = rollout_plugin_describe(term_plugin.key); return 1; }
-    if (term_every > 0 && term_plugin_state < 0) { if (text) *text = term_msg; return -1; }
-    if (plugin_state > 0) { if (text) *text = rollout_plugin_describe(plugin.key); return 1; }
-    if (plugin_state < 0) { if (text) *text = plugin_msg; return -1; }
+    for (const RolloutVariant* v : {&variant_of(false), &variant[0][0]}) {  // (the refreshing object where one was asked for, else the plain one)
+      if (v->state > 0) { if (text) *text = rollout_plugin_describe(v->plugin.key); return 1; }
+      if (v->state < 0) { if (text) *text = v->msg; return -1; }
+    }
     if (!fused_rollout_ok()) { if (text) *text = "no fused roll-out for this configuration (per-step launches)"; return 2; }
     if (text) *text = "built-in instantiation of libkoopmpc.so";
     return 0;
   }
   // io32: the caller-owned panels (X, ref, Ulog, Xlog, U0out, Useqout) are float32 -- the call comes from a KMPC_F32 handle's core
-  int rollout_fused(int plant, void* X, const void* ref, int rpt, int steps, int step0, int switch_step, double hs,
+  int rollout_fused(const StepCtx& ctx, int plant, void* X, const void* ref, int rpt, int steps, int step0, int switch_step, double hs,
                     void* Ulog, void* Xlog, int32_t* st, int32_t* it, hipStream_t s, void* U0out = nullptr,
                     void* Useqout = nullptr, bool io32 = false) {
     int rc = check_lift_ready();
@@ -1160,7 +1174,7 @@ struct Impl : kmpc_handle {
       if (core) {
         if ((rc = ensure_image(s))) return rc;
         core->prof = prof;
-        rc = core->rollout_fused(plant, X, ref, rpt, steps, step0, switch_step, hs, Ulog, Xlog, st, it, s, U0out, Useqout, true);
+        rc = core->rollout_fused(ctx, plant, X, ref, rpt, steps, step0, switch_step, hs, Ulog, Xlog, st, it, s, U0out, Useqout, true);
         if (rc) { err = core->err; return rc; }
         have_prev = core->have_prev; rls_fresh = core->rls_fresh; cur = core->cur;
         return 0;
@@ -1179,7 +1193,7 @@ struct Impl : kmpc_handle {
       if ((rc = pack_encoder(s))) return rc;
       r.lift_rbf = 0;
       r.W1 = dW1; r.b1 = db1; r.Whp[0] = dWhp[0]; r.Whp[1] = dWhp[1]; r.bh[0] = dbh[0]; r.bh[1] = dbh[1];
-      r.Wop = dWop; r.bo = dbo; r.Hp = Hp; r.Lp = Lp; r.KS = (hid + 3) / 4; r.nhh = cfg.layers - 1;
+      r.Wop = dWop; r.bo = dbo; r.Hp = enc.Hp; r.Lp = enc.Lp; r.KS = enc.KS; r.nhh = cfg.layers - 1;
     } else {
       r.lift_rbf = 1;
       r.cx = dcx; r.eps = (T)cfg.rbf_eps; r.rbf_matlab = cfg.lift_kind == KMPC_LIFT_RBF_MATLAB ? 1 : 0;
@@ -1191,7 +1205,7 @@ struct Impl : kmpc_handle {
     r.U_log = (T*)Ulog; r.X_log = (T*)Xlog;
     r.io_f32 = io32 ? 1 : 0;
     if (io32 && !r.s.U0) r.s.U0 = dU0;
-    if (dg_call) { r.diag = 1; r.Psi_log = dg_log[0]; r.dA_log = dg_log[1]; r.dB_log = dg_log[2]; r.dC_log = dg_log[3]; }
+    if (ctx.diag) { r.diag = 1; r.Psi_log = (T*)ctx.diag->Psi; r.dA_log = (T*)ctx.diag->dA; r.dB_log = (T*)ctx.diag->dB; r.dC_log = (T*)ctx.diag->dC; }
     if constexpr (sizeof(T) == 8) {
       if (term_every > 0) {
         if (io32) FAIL(-3, "the per-step terminal refresh is a float64 feature");
@@ -1201,6 +1215,8 @@ struct Impl : kmpc_handle {
         r.s.Wterm = dWtB; r.s.wterm_per_traj = 1;
       }
     }
+    // (the card deal across the workgroups where the batch allows it: whole workgroups; the rank kernel is O(B^2 / lanes))
+    const bool global_place = cfg.lift_kind == KMPC_LIFT_MLP && (B & 15) == 0 && B <= (1 << 20);
     if (!dbg_env("KMPC_ROLLOUT_NO_PLACE")) {  // (the trajectories' solver work of the previous launch: RolloutArgs::work)
       if (!dWork) {
         HIPCHK(hipMalloc(&dWork, sizeof(int32_t) * (size_t)B));
@@ -1209,8 +1225,7 @@ struct Impl : kmpc_handle {
       r.work = dWork;
       static const int tail = dbg_env("KMPC_PLACE_TAIL") ? atoi(dbg_env("KMPC_PLACE_TAIL")) : 5;  // (measurement aid; 0 = the whole launch)
       r.work_tail = tail;
-      // ... across the workgroups too where the batch allows the card deal (whole workgroups; the rank kernel is O(B^2 / lanes))
-      if (place_valid && cfg.lift_kind == KMPC_LIFT_MLP && (B & 15) == 0 && B <= (1 << 20) && !dbg_env("KMPC_ROLLOUT_NO_GLOBAL_PLACE")) r.perm = dPerm;
+      if (place_valid && global_place && !dbg_env("KMPC_ROLLOUT_NO_GLOBAL_PLACE")) r.perm = dPerm;
       // (work and perm were written on the stream of the previous call: a call on another stream waits for them -- a torn perm would
       //  hand one trajectory to two waves and skip another: ADVICE r4)
       if (evPlace && place_stream != s) HIPCHK(hipStreamWaitEvent(s, evPlace, 0));
@@ -1221,25 +1236,13 @@ struct Impl : kmpc_handle {
         r.img = dImg; r.img_stride = sImg;
       } else if ((rc = ensure_dense(s, true))) return rc;
     }
-    const bool rec = prof && ev_used + 3 <= EV_CAP;
-    if (rec) {
-      while (ev.size() < ev_used + 3) {
-        hipEvent_t e;
-        HIPCHK(hipEventCreate(&e));
-        ev.push_back(e);
-      }
-      HIPCHK(hipEventRecord(ev[ev_used], s));
-      HIPCHK(hipEventRecord(ev[ev_used + 1], s));  // (no separate lift kernel)
-    }
-    HIPCHK(launch_rollout_fused<T>(r, s, dg_call ? (term_every > 0 ? &diag_term_plugin : &diag_plugin) : (term_every > 0 ? &term_plugin : &plugin)));
+    bool rec;
+    if ((rc = prof_begin(s, &rec)) || (rec && (rc = prof_mid(s)))) return rc;  // (no separate lift kernel)
+    HIPCHK(launch_rollout_fused<T>(r, s, &variant_of(ctx.diag != nullptr).plugin));
     // (profiling: the closing event sits right behind the roll-out kernel -- until round 5 it sat behind the rank pass below, whose
     //  9 us at B = 4096 were counted into "the dominant kernel's duration": rocprofv3 0.630 ms against 0.647 ms from these events)
-    if (rec) {
-      HIPCHK(hipEventRecord(ev[ev_used + 2], s));
-      ev_used += 3;
-      prof_steps += steps;
-    }
-    if (r.work && steps >= 4 && cfg.lift_kind == KMPC_LIFT_MLP && (B & 15) == 0 && B <= (1 << 20)) {
+    if (rec && (rc = prof_end(s, steps))) return rc;
+    if (r.work && steps >= 4 && global_place) {
       if (!dPerm) HIPCHK(hipMalloc(&dPerm, sizeof(int32_t) * (size_t)B * 3));  // (perm, then the sort's two ping-pong buffers)
       HIPCHK(launch_place(dWork, B, dPerm, reinterpret_cast<uint32_t*>(dPerm + B), s));  // (the next launch's deal: RolloutArgs::perm)
       place_valid = true;
@@ -1260,26 +1263,26 @@ struct Impl : kmpc_handle {
   }
 
   T* dU0 = nullptr;  // rollout scratch [B]
-  bool accumulate = false;
-  int fuse_plant = -1, fuse_switched = 0;  // rollouts: the step kernel advances the plant itself
-  double fuse_h = 0.05;
-  void* fuse_X = nullptr;  // (shared-model solve with the plant inside)
   int rollout(int plant, void* X, const void* ref, int rpt, int steps, int step0, int switch_step, double hs,
               void* Ulog, void* Xlog, int32_t* st, int32_t* it, hipStream_t s) override {
+    return rollout_impl(StepCtx{}, plant, X, ref, rpt, steps, step0, switch_step, hs, Ulog, Xlog, st, it, s);
+  }
+  int rollout_impl(const StepCtx& ctx, int plant, void* X, const void* ref, int rpt, int steps, int step0, int switch_step, double hs,
+                   void* Ulog, void* Xlog, int32_t* st, int32_t* it, hipStream_t s) {
     if (!X || !ref || steps < 0) FAIL(-3, "kmpc_rollout: bad arguments");
     if (!dU0) HIPCHK(hipMalloc(&dU0, sizeof(T) * (size_t)B));
     if (n != 2) FAIL(-3, "plants are two-state systems");
     if (!plant_id_ok(plant)) FAIL(-3, "unknown plant");
     // (the fused roll-out with the MLP lift accumulates status / iterations in LDS and WRITES them when it ends: no zeroing
     //  launches in front of it -- two of the ~70 us a 20-step call spends outside its kernel)
-    const bool fused = fused_rollout_ok() && (!dg_call || diag_fused_ready());  // (kmpc_rollout_diag: its fused route needs the DIAG plug-in)
+    const bool fused = fused_rollout_ok() && (!ctx.diag || diag_fused_ready());  // (kmpc_rollout_diag: its fused route needs the DIAG plug-in)
     const bool kernel_writes_totals = steps > 0 && fused && cfg.lift_kind == KMPC_LIFT_MLP;
     if (!kernel_writes_totals) {
       if (st) HIPCHK(hipMemsetAsync(st, 0, sizeof(int32_t) * (size_t)B, s));
       if (it) HIPCHK(hipMemsetAsync(it, 0, sizeof(int32_t) * (size_t)B, s));
     }
     if (steps > 0 && fused)
-      return rollout_fused(plant, X, ref, rpt, steps, step0, switch_step, hs, Ulog, Xlog, st, it, s);
+      return rollout_fused(ctx, plant, X, ref, rpt, steps, step0, switch_step, hs, Ulog, Xlog, st, it, s);
     if (steps == 0 && fused) {
       // a call without steps brings the handle into the form the fused roll-out works on (the wave image of a state that was
       // set, restored or stepped through the dense blocks): set-up that the next kmpc_rollout would otherwise pay
@@ -1295,14 +1298,9 @@ struct Impl : kmpc_handle {
     for (int i = 0; i < steps; ++i) {
       const int gi = step0 + i;
       T* u = Ulog ? (T*)Ulog + (size_t)i * B : dU0;
-      if (n != 2) FAIL(-3, "plants are two-state systems");
-      if (!plant_id_ok(plant)) FAIL(-3, "unknown plant");
-      if (dg_call) { const int rcd = diag_before_step(X, i, s); if (rcd) return rcd; }
-      accumulate = true;
-      fuse_plant = plant; fuse_switched = (switch_step >= 0 && gi >= switch_step) ? 1 : 0; fuse_h = hs;
-      int rc = step(X, ref, rpt, u, nullptr, st, it, s);  // lift kernel + fused RLS/condense/QP/plant kernel
-      accumulate = false;
-      fuse_plant = -1;
+      if (ctx.diag) { const int rcd = diag_before_step(*ctx.diag, X, i, s); if (rcd) return rcd; }
+      // lift kernel + fused RLS/condense/QP/plant kernel
+      int rc = step_impl(StepCtx{true, plant, (switch_step >= 0 && gi >= switch_step) ? 1 : 0, hs, X, nullptr}, X, ref, rpt, u, nullptr, st, it, s);
       if (rc) return rc;
       if (Xlog) HIPCHK(hipMemcpyAsync((T*)Xlog + (size_t)i * n * B, X, sizeof(T) * (size_t)n * B,
                                       hipMemcpyDeviceToDevice, s));
@@ -1369,12 +1367,12 @@ struct Impl : kmpc_handle {
       if (have_prev && !two && cfg.lift_kind == KMPC_LIFT_MLP) {
         if ((rc = check_lift_ready())) return rc;
         LiftArgs<T> a{};
-        a.B = B; a.n = n; a.L = L; a.hidden = hid; a.nlayers = cfg.layers;
+        a.B = B; a.n = n; a.L = L; a.hidden = enc.hid; a.nlayers = cfg.layers;
         a.X = (const T*)X; a.Psi = psi_now; a.ps_l = 1; a.ps_b = L;
         a.W1 = dW1; a.b1 = db1; a.Wh[0] = dWh[0]; a.Wh[1] = dWh[1]; a.bh[0] = dbh[0]; a.bh[1] = dbh[1];
-        a.Wo = dWo; a.bo = dbo; a.Hp = Hp; a.Lp = Lp;
+        a.Wo = dWo; a.bo = dbo; a.Hp = enc.Hp; a.Lp = enc.Lp;
         if ((rc = pack_encoder(s))) return rc;
-        a.Whp[0] = dWhp[0]; a.Whp[1] = dWhp[1] ? dWhp[1] : dWhp[0]; a.Wop = dWop; a.KSp = (hid + 3) / 4;
+        a.Whp[0] = dWhp[0]; a.Whp[1] = dWhp[1] ? dWhp[1] : dWhp[0]; a.Wop = dWop; a.KSp = enc.KS;
         if (lift_gram_available(a)) {
           int nb = 0;
           HIPCHK(launch_lift_gram(a, g, &nb, s));
@@ -1397,10 +1395,7 @@ struct Impl : kmpc_handle {
     if (!X) FAIL(-3, "kmpc_shared_solve_plant: null pointer");
     if (n != 2) FAIL(-3, "plants are two-state systems");
     if (!plant_id_ok(plant)) FAIL(-3, "unknown plant");
-    fuse_plant = plant; fuse_switched = switched ? 1 : 0; fuse_h = hstep; fuse_X = X;
-    const int rc = shared_solve(delta, ref, U0, Useq, st, it, s);
-    fuse_plant = -1; fuse_X = nullptr;
-    return rc;
+    return shared_solve_impl(StepCtx{false, plant, switched ? 1 : 0, hstep, X, nullptr}, delta, ref, U0, Useq, st, it, s);
   }
   // kmpc_shared_rollout: the stages of the shared-model step, `steps` times, on one stream, the collective between them
   double* dDelta = nullptr;  // this rank's Gram sums of a step (all-reduced in place)
@@ -1429,9 +1424,7 @@ struct Impl : kmpc_handle {
         if (nr != ncclSuccess) FAIL(-(2000 + (int)nr), "kmpc_shared_rollout: ncclAllReduce failed");
       }
       T* const u = Ulog ? (T*)Ulog + (size_t)i * B : (U0out ? (T*)U0out : dU0);
-      accumulate = true;
-      rc = shared_solve_plant(dDelta, ref, u, Useq, st, it, plant, X, (switch_step >= 0 && gi >= switch_step) ? 1 : 0, hstep, s);
-      accumulate = false;
+      rc = shared_solve_impl(StepCtx{true, plant, (switch_step >= 0 && gi >= switch_step) ? 1 : 0, hstep, X, nullptr}, dDelta, ref, u, Useq, st, it, s);
       if (rc) return rc;
       if (Xlog) HIPCHK(hipMemcpyAsync((T*)Xlog + (size_t)i * n * B, X, sizeof(T) * (size_t)n * B, hipMemcpyDeviceToDevice, s));
     }
@@ -1439,8 +1432,10 @@ struct Impl : kmpc_handle {
       HIPCHK(hipMemcpyAsync(U0out, (T*)Ulog + (size_t)(steps - 1) * B, sizeof(T) * (size_t)B, hipMemcpyDeviceToDevice, s));
     return 0;
   }
-  int shared_solve(const double* delta, const void* ref, void* U0, void* Useq, int32_t* st, int32_t* it,
-                   hipStream_t s) override {
+  int shared_solve(const double* delta, const void* ref, void* U0, void* Useq, int32_t* st, int32_t* it, hipStream_t s) override {
+    return shared_solve_impl(StepCtx{}, delta, ref, U0, Useq, st, it, s);
+  }
+  int shared_solve_impl(const StepCtx& ctx, const double* delta, const void* ref, void* U0, void* Useq, int32_t* st, int32_t* it, hipStream_t s) {
     if (!delta || !ref || !U0) FAIL(-3, "kmpc_shared_solve: null pointer");
     if (have_wterm && wterm_from_dare && wterm_per_traj)
       FAIL(-3, "kmpc_shared_solve: per-trajectory terminal blocks do not apply to the shared model (kmpc_terminal_from_dare with per_trajectory = 0)");
@@ -1504,19 +1499,11 @@ struct Impl : kmpc_handle {
     a.psi_now = dPsi[cur]; a.pn_sl = 1; a.pn_sb = L;
     a.U0 = (T*)U0; a.Useq = (T*)Useq; a.u_store = dUprev; a.status = st; a.iters = it;
     a.x_warm = cfg.cold_start ? nullptr : dWarm;
-    a.accumulate = accumulate ? 1 : 0;  // (kmpc_shared_rollout: worst status / total Newton solves over the steps)
+    a.accumulate = ctx.accumulate ? 1 : 0;  // (kmpc_shared_rollout: worst status / total Newton solves over the steps)
     // (kmpc_shared_solve_plant: the solve also advances every trajectory's plant with its u_k, as the roll-outs do)
-    if (fuse_plant >= 0) { a.plant = fuse_plant; a.plant_switched = fuse_switched; a.plant_h = (T)fuse_h; a.X_rw = (T*)fuse_X; }
-    const bool rec = prof && ev_used + 3 <= EV_CAP;  // (profiling: the QP launch of the shared-model step)
-    if (rec) {
-      while (ev.size() < ev_used + 3) {
-        hipEvent_t e;
-        HIPCHK(hipEventCreate(&e));
-        ev.push_back(e);
-      }
-      HIPCHK(hipEventRecord(ev[ev_used], s));
-      HIPCHK(hipEventRecord(ev[ev_used + 1], s));
-    }
+    if (ctx.plant >= 0) { a.plant = ctx.plant; a.plant_switched = ctx.switched; a.plant_h = (T)ctx.h; a.X_rw = (T*)ctx.X_rw; }
+    bool rec;  // (profiling: the QP launch of the shared-model step)
+    if ((rc = prof_begin(s, &rec)) || (rec && (rc = prof_mid(s)))) return rc;
     // the trajectories whose unconstrained minimiser lies inside the box are finished 16 per wave on the matrix cores
     // (shared_fast_kernel); the solve-only kernel then only runs for the flagged rest
     const bool no_fast = dbg_env("KMPC_SHARED_NO_FAST") != nullptr;  // measurement / test aid (read per call): every trajectory through the QP kernel
@@ -1537,11 +1524,7 @@ struct Impl : kmpc_handle {
       a.qp_need = dNeed;
     }
     HIPCHK(launch_step<T>(a, threads, s));
-    if (rec) {
-      HIPCHK(hipEventRecord(ev[ev_used + 2], s));
-      ev_used += 3;
-      prof_steps += 1;
-    }
+    if (rec && (rc = prof_end(s, 1))) return rc;
     have_prev = true;
     cur ^= 1;
     return 0;
@@ -1838,42 +1821,40 @@ int kmpc_set_terminal_refresh(kmpc_handle* h, int every, const double* Q, double
 int kmpc_rollout_is_fused(const kmpc_handle* h) { NN(h); return h->rollout_is_fused(); }
 // Makes (or finds) the plug-in a handle of this configuration would load -- no device needed: hipcc cross-compiles.  For builds that
 // want the kernel cache filled before the first kmpc_create (__graft_entry__.build(), an installer, the first rank of a node).
-int kmpc_rollout_plugin_prebuild(int n, int L, int N, int out_rows, int lift_kind, int hidden_eff, int batch, int dtype, char* text, int text_bytes) {
-  auto say = [&](const std::string& t) { if (text && text_bytes > 0) snprintf(text, (size_t)text_bytes, "%s", t.c_str()); };
-  const bool rbf = lift_kind != KMPC_LIFT_MLP;
-  const int q = out_rows > 0 ? out_rows : n;
-  if (n != 2 || L < 1 || N < 1 || batch < 1 || (!rbf && (hidden_eff < 1 || hidden_eff > 128)) || (dtype != KMPC_F32 && dtype != KMPC_F64)) { say("bad arguments"); return -3; }
-  const int Hp = hidden_eff <= 112 ? 112 : 128, Lp = ((L + 15) / 16) * 16, KS = (hidden_eff + 3) / 4;
-  const bool io32 = dtype == KMPC_F32;
-  if (!(io32 ? rollout_io32_available(n, L, N, q, rbf) : rollout_fused_available<double>(n, L, N, q, 64, rbf))) { say("no fused roll-out for this configuration"); return 2; }
+static void put_text(char* text, int text_bytes, const std::string& t) { if (text && text_bytes > 0) snprintf(text, (size_t)text_bytes, "%s", t.c_str()); }
+// 1: made or found (*text: the object), -1: failed (*text: why), 0: the configuration has no object of this variant
+static int prebuild_variant(int n, int L, int N, int q, bool rbf, int hidden_eff, int batch, bool io32, bool term, bool diag, std::string* text) {
+  const EncoderShape e = encoder_shape(hidden_eff, 0, n, L);
   RolloutPluginKey k{};
-  if (!rollout_plugin_key(n, L, N, q, rbf, Lp, KS, Hp, batch, io32, &k)) { say("built-in instantiation of libkoopmpc.so"); return 0; }
-  std::string err;
-  if (!rollout_plugin_get(k, &err)) { say(err); return -1; }
-  say(rollout_plugin_describe(k));
+  if (!rollout_plugin_key(n, L, N, q, rbf, e.Lp, e.KS, e.Hp, batch, io32, &k, term, diag)) return 0;
+  if (!rollout_plugin_get(k, text)) return -1;
+  *text = rollout_plugin_describe(k);
   return 1;
 }
+int kmpc_rollout_plugin_prebuild(int n, int L, int N, int out_rows, int lift_kind, int hidden_eff, int batch, int dtype, char* text, int text_bytes) {
+  auto say = [&](int code, const std::string& t) { put_text(text, text_bytes, t); return code; };
+  const bool rbf = lift_kind != KMPC_LIFT_MLP, io32 = dtype == KMPC_F32;
+  const int q = out_rows > 0 ? out_rows : n;
+  if (n != 2 || L < 1 || N < 1 || batch < 1 || (!rbf && (hidden_eff < 1 || hidden_eff > 128)) || (dtype != KMPC_F32 && dtype != KMPC_F64)) return say(-3, "bad arguments");
+  if (!(io32 ? rollout_io32_available(n, L, N, q, rbf) : rollout_fused_available<double>(n, L, N, q, 64, rbf))) return say(2, "no fused roll-out for this configuration");
+  std::string t;
+  const int rc = prebuild_variant(n, L, N, q, rbf, hidden_eff, batch, io32, false, false, &t);
+  return rc == 0 ? say(0, "built-in instantiation of libkoopmpc.so") : say(rc, t);
+}
 int kmpc_rollout_diag_plugin_prebuild(int n, int L, int N, int out_rows, int lift_kind, int hidden_eff, int batch, int with_term, char* text, int text_bytes) {
-  auto say = [&](const std::string& t) { if (text && text_bytes > 0) snprintf(text, (size_t)text_bytes, "%s", t.c_str()); };
+  auto say = [&](int code, const std::string& t) { put_text(text, text_bytes, t); return code; };
   const bool rbf = lift_kind != KMPC_LIFT_MLP;
   const int q = out_rows > 0 ? out_rows : n;
-  if (n != 2 || L < 1 || N < 1 || batch < 1 || (!rbf && (hidden_eff < 1 || hidden_eff > 128))) { say("bad arguments"); return -3; }
-  const int Hp = hidden_eff <= 112 ? 112 : 128, Lp = ((L + 15) / 16) * 16, KS = (hidden_eff + 3) / 4;
-  RolloutPluginKey k{};
-  if (!rollout_fused_available<double>(n, L, N, q, 64, rbf) || !rollout_plugin_key(n, L, N, q, rbf, Lp, KS, Hp, batch, false, &k, with_term != 0, true)) {
-    say("no fused diagnostics variant for this configuration (per-step launches)");
-    return 2;
-  }
-  std::string err;
-  if (!rollout_plugin_get(k, &err)) { say(err); return -1; }
-  say(rollout_plugin_describe(k));
-  return 1;
+  if (n != 2 || L < 1 || N < 1 || batch < 1 || (!rbf && (hidden_eff < 1 || hidden_eff > 128))) return say(-3, "bad arguments");
+  std::string t;
+  const int rc = rollout_fused_available<double>(n, L, N, q, 64, rbf) ? prebuild_variant(n, L, N, q, rbf, hidden_eff, batch, false, with_term != 0, true, &t) : 0;
+  return rc == 0 ? say(2, "no fused diagnostics variant for this configuration (per-step launches)") : say(rc, t);
 }
 int kmpc_rollout_plugin_status(const kmpc_handle* h, char* text, int text_bytes) {
   if (!h) return -100;
   std::string t;
   const int rc = h->rollout_plugin_status(&t);
-  if (text && text_bytes > 0) { snprintf(text, (size_t)text_bytes, "%s", t.c_str()); }
+  put_text(text, text_bytes, t);
   return rc;
 }
 // The placement pass of the fused roll-out as a function of its own (tests, tools): perm_dev receives, in its first B entries, the

@@ -225,6 +225,13 @@ bool rollout_builtin(int L, int N, int q, bool io32);  // libkoopmpc.so itself h
 //  diagnostics logs -- likewise, float64 register-state sets only)
 bool rollout_plugin_key(int n, int L, int N, int q, bool rbf, int Lp, int KS, int Hp, int B, bool io32, RolloutPluginKey* out, bool term = false,
                         bool diag = false);
+// the MLP encoder as the kernels see it: effective hidden width (lift_offset = 2 carries x on 2 n more units), its padding, the padded
+// output rows and the MFMA k-steps of 4 over the hidden width
+struct EncoderShape { int hid, Hp, Lp, KS; };
+inline EncoderShape encoder_shape(int hidden, int lift_offset, int n, int L) {
+  const int hid = hidden + (lift_offset == 2 ? 2 * n : 0);
+  return {hid, hid <= 112 ? 112 : 128, ((L + 15) / 16) * 16, (hid + 3) / 4};
+}
 // wave image of one trajectory's state (step_v2.h): [column pair][slot][2] doubles, layer 2 then layer 1
 struct V2Dims {
   int L, n, p, cp, s2, s1;

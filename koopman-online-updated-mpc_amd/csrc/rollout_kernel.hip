@@ -798,6 +798,28 @@ template <int L_, int N_, int Q_, typename IOT = double> static hipError_t launc
 #endif  // KMPC_ROLLOUT_JIT_TU
 }
 
+// The dimension sets (L, N, q) whose instantiations libkoopmpc.so holds itself (BASELINE.json's configurations, the reference's scripts),
+// float64 and float32 panels: rollout_builtin and the two dispatches below are generated from these lists.  Every other set of
+// rollout_plugin_dims gets its kernel as a plug-in when a handle is created (rollout_plugin.hip).  A development build
+// (KMPC_DEV_CFG2_ONLY) holds the sets outside KMPC_FULL_BUILD only, with KMPC_DEV_LIFT the y = psi sets as well.
+#ifndef KMPC_DEV_CFG2_ONLY
+#define KMPC_FULL_BUILD(...) __VA_ARGS__
+#define KMPC_LIFT_BUILD(...) __VA_ARGS__
+#else
+#define KMPC_FULL_BUILD(...)
+#ifdef KMPC_DEV_LIFT
+#define KMPC_LIFT_BUILD(...) __VA_ARGS__
+#else
+#define KMPC_LIFT_BUILD(...)
+#endif
+#endif
+#define KMPC_ROLLOUT_SETS_F64(X)                                                        \
+  X(20, 20, 2) /* BASELINE cfg2 */ X(8, 30, 2) /* BASELINE cfg3 (RBF lift, y = Cx) */   \
+  KMPC_LIFT_BUILD(X(8, 10, 8) X(8, 30, 8))                                              \
+  KMPC_FULL_BUILD(X(8, 10, 2) X(10, 20, 1) /* Tank_System.m */ X(20, 30, 2) /* cfg3 sizes, y = Cx */ X(32, 40, 2) /* cfg4 sizes */ X(32, 40, 1))
+#define KMPC_ROLLOUT_SETS_F32(X) X(20, 20, 2) /* BASELINE cfg2 ("fp32") */ KMPC_FULL_BUILD(X(8, 30, 2) X(8, 10, 2) X(10, 20, 1) X(20, 30, 2))
+#define KMPC_SET_IS(L_, N_, q_) || (L == L_ && N == N_ && q == q_)
+#define KMPC_SET_LAUNCH(L_, N_, q_) if (a.s.L == L_ && a.s.N == N_ && a.s.q == q_) return launch_rollout_impl<L_, N_, q_, IOT>(a, s);
 #if defined(KMPC_ROLLOUT_JIT_TU)
 // (the plug-in's entry point: rollout_jit.hip)
 #elif defined(KMPC_ROLLOUT_IO32_TU)
@@ -806,13 +828,8 @@ hipError_t launch_rollout_io32(const RolloutArgs<double>& a, hipStream_t s) {
   if (a.s.B <= 0 || a.steps <= 0) return hipSuccess;
   if (!a.lift_rbf && (a.Hp > 128 || (a.Hp & 15) || a.Lp > 64 || a.KS > 32 || a.nhh < 0 || a.nhh > 2 || a.s.n > 4))
     return hipErrorInvalidValue;
-  if (a.s.L == 20 && a.s.N == 20 && a.s.q == 2) return launch_rollout_impl<20, 20, 2, float>(a, s);  // BASELINE cfg2 ("fp32")
-#ifndef KMPC_DEV_CFG2_ONLY
-  if (a.s.L == 8 && a.s.N == 30 && a.s.q == 2) return launch_rollout_impl<8, 30, 2, float>(a, s);
-  if (a.s.L == 8 && a.s.N == 10 && a.s.q == 2) return launch_rollout_impl<8, 10, 2, float>(a, s);
-  if (a.s.L == 10 && a.s.N == 20 && a.s.q == 1) return launch_rollout_impl<10, 20, 1, float>(a, s);
-  if (a.s.L == 20 && a.s.N == 30 && a.s.q == 2) return launch_rollout_impl<20, 30, 2, float>(a, s);
-#endif
+  using IOT = float;
+  KMPC_ROLLOUT_SETS_F32(KMPC_SET_LAUNCH)
   return hipErrorInvalidValue;
 }
 #else
@@ -821,21 +838,10 @@ hipError_t launch_rollout_io32(const RolloutArgs<double>&, hipStream_t) { return
 #else
 hipError_t launch_rollout_io32(const RolloutArgs<double>& a, hipStream_t s);
 #endif
-// the dimension sets whose instantiations libkoopmpc.so holds itself (BASELINE.json's configurations, the reference's scripts); every
-// other set of rollout_plugin_dims gets its kernel as a plug-in when a handle is created (rollout_plugin.hip)
 bool rollout_builtin(int L, int N, int q, bool io32) {
   static const bool force = dbg_env("KMPC_FORCE_PLUGIN") != nullptr;  // measurement aid: every set on a plug-in compiled from the shipped sources
   if (force) return false;
-#ifdef KMPC_DEV_CFG2_ONLY
-  if (io32) return L == 20 && N == 20 && q == 2;
-  return (L == 20 && N == 20 && q == 2) || (L == 8 && N == 30 && q == 2);
-#endif
-  if (io32)
-    return (L == 20 && N == 20 && q == 2) || (L == 8 && N == 30 && q == 2) || (L == 8 && N == 10 && q == 2) || (L == 10 && N == 20 && q == 1) ||
-           (L == 20 && N == 30 && q == 2);
-  return (L == 20 && N == 20 && q == 2) || (L == 8 && N == 10 && q == 2) || (L == 8 && N == 10 && q == 8) ||
-         (L == 8 && N == 30 && q == 8) || (L == 8 && N == 30 && q == 2) || (L == 10 && N == 20 && q == 1) ||
-         (L == 20 && N == 30 && q == 2) || (L == 32 && N == 40 && q == 2) || (L == 32 && N == 40 && q == 1);
+  return io32 ? (false KMPC_ROLLOUT_SETS_F32(KMPC_SET_IS)) : (false KMPC_ROLLOUT_SETS_F64(KMPC_SET_IS));
 }
 // true: a KMPC_F32 handle of this dimension set has the fused roll-out with float32 panels around the float64 state
 bool rollout_io32_available(int n, int L, int N, int q, bool rbf) {
@@ -876,19 +882,8 @@ template <> hipError_t launch_rollout_fused<double>(const RolloutArgs<double>& a
     return hipErrorInvalidValue;
   if (a.term_every > 0 || a.diag || !rollout_builtin(a.s.L, a.s.N, a.s.q, a.io_f32 != 0)) return launch_rollout_plugin(a, plugin, s);
   if (a.io_f32) return launch_rollout_io32(a, s);
-  if (a.s.L == 20 && a.s.N == 20 && a.s.q == 2) return launch_rollout_impl<20, 20, 2>(a, s);
-  if (a.s.L == 8 && a.s.N == 30 && a.s.q == 2) return launch_rollout_impl<8, 30, 2>(a, s);  // BASELINE cfg3 (RBF lift, y = Cx)
-#if !defined(KMPC_DEV_CFG2_ONLY) || defined(KMPC_DEV_LIFT)  // (development builds compile the cfg2 / cfg3 instantiations only)
-  if (a.s.L == 8 && a.s.N == 10 && a.s.q == 8) return launch_rollout_impl<8, 10, 8>(a, s);
-  if (a.s.L == 8 && a.s.N == 30 && a.s.q == 8) return launch_rollout_impl<8, 30, 8>(a, s);
-#endif
-#ifndef KMPC_DEV_CFG2_ONLY
-  if (a.s.L == 8 && a.s.N == 10 && a.s.q == 2) return launch_rollout_impl<8, 10, 2>(a, s);
-  if (a.s.L == 10 && a.s.N == 20 && a.s.q == 1) return launch_rollout_impl<10, 20, 1>(a, s);  // Tank_System.m dimensions
-  if (a.s.L == 20 && a.s.N == 30 && a.s.q == 2) return launch_rollout_impl<20, 30, 2>(a, s);  // BASELINE cfg3 sizes, y = Cx
-  if (a.s.L == 32 && a.s.N == 40 && a.s.q == 2) return launch_rollout_impl<32, 40, 2>(a, s);  // BASELINE cfg4 sizes
-  if (a.s.L == 32 && a.s.N == 40 && a.s.q == 1) return launch_rollout_impl<32, 40, 1>(a, s);
-#endif
+  using IOT = double;
+  KMPC_ROLLOUT_SETS_F64(KMPC_SET_LAUNCH)
   return hipErrorInvalidValue;
 }
 template <> hipError_t launch_rollout_fused<float>(const RolloutArgs<float>&, hipStream_t, const RolloutPlugin*) { return hipErrorInvalidValue; }

@@ -45,17 +45,12 @@ def prebuild(sets=None, verbose=False):
     out = []
     for st in ((DEFAULT_SETS + DIAG_SETS) if sets is None else sets):
         n, L, N, out_rows, lift, hidden, batch, dtype = st
-        if dtype.endswith("+diag"):
-            buf = C.create_string_buffer(1024)
-            code = int(lib.kmpc_rollout_diag_plugin_prebuild(n, L, N, out_rows, _KIND[lift], hidden, batch, int("+term" in dtype), buf, len(buf)))
-            text = buf.value.decode("utf-8", "replace")
-            if verbose:
-                print("plug-in %s: %d %s" % (st, code, text))
-            out.append((st, code, text))
-            continue
-        kind = _KIND[lift]
         buf = C.create_string_buffer(1024)
-        code = int(lib.kmpc_rollout_plugin_prebuild(n, L, N, out_rows, kind, hidden, batch, _ffi.KMPC_F64 if dtype == "f64" else _ffi.KMPC_F32, buf, len(buf)))
+        if dtype.endswith("+diag"):
+            fn, last = lib.kmpc_rollout_diag_plugin_prebuild, int("+term" in dtype)
+        else:
+            fn, last = lib.kmpc_rollout_plugin_prebuild, _ffi.KMPC_F64 if dtype == "f64" else _ffi.KMPC_F32
+        code = int(fn(n, L, N, out_rows, _KIND[lift], hidden, batch, last, buf, len(buf)))
         text = buf.value.decode("utf-8", "replace")
         if verbose:
             print("plug-in %s: %d %s" % (st, code, text))

@@ -386,6 +386,65 @@ def test_raw_c_abi(torch_mod, KM):
     assert lib.kmpc_set_rollout_diagnostics(msh.h, 1) < 0 and b"shared-model" in lib.kmpc_last_error(msh.h)
 
 
+# ------------------------------------------------------------------ arming order, refused calls
+def test_diagnostics_armed_before_the_terminal_refresh(torch_mod, KM):
+    """kmpc_set_rollout_diagnostics FIRST, kmpc_set_terminal_refresh after it (test_raw_c_abi arms in the other order): the refresh setter
+    loads the variant that has both, the status text names it, and the diagnostics roll-out (6 steps from iteration 99, switch at 102)
+    equals a plain roll-out on a twin that only has the refresh, bit for bit; so does a second window after the diagnostics were
+    switched off and on again."""
+    torch = torch_mod
+    g, w, model0, (md, mt), X0, r = _main_case(torch, KM)
+    assert md.set_rollout_diagnostics(True) == 0
+    for mm in (md, mt):
+        mm.set_terminal_refresh(every=1)
+    code, text = md.rollout_plugin_status()
+    assert code == 1 and "_f64_term_diag_" in text.split("kmpc_rollout_diag")[1], (code, text)
+    Xd, Xt = _t(torch, X0), _t(torch, X0)
+    for window, step0 in enumerate((99, 105)):
+        if window == 1:
+            assert md.set_rollout_diagnostics(False) == 0 and md.set_rollout_diagnostics(True) == 0
+        Ud, Xld, dg = md.rollout("duffing", Xd, r, 6, step0=step0, switch_step=102, log=True, diagnostics=True)
+        Ut, Xlt = mt.rollout("duffing", Xt, r, 6, step0=step0, switch_step=102, log=True)
+        assert torch.equal(Ud, Ut) and torch.equal(Xld, Xlt) and torch.equal(Xd, Xt) and torch.equal(md.status, mt.status), window
+        assert not any(bool(torch.isnan(v).any()) for v in dg.values())
+
+
+def test_a_refused_call_leaves_nothing_behind(torch_mod, KM):
+    """Calls the argument checks refuse before any launch (kmpc_rollout_diag with X = NULL, then with steps = -1; kmpc_shared_solve_plant
+    with X = NULL; each returns -3) leave no trace in the handle: the plain rollout(log=True), the step() calls and the state_dict()
+    that follow equal those of an untouched twin bit for bit."""
+    torch = torch_mod
+    g, w, model0, (m, twin), X0, r = _main_case(torch, KM)
+    B, steps, lib = 64, 6, m.lib
+    assert m.set_rollout_diagnostics(True) == 0
+    rr, per = m._ref(r)
+    kw = dict(dtype=torch.float64, device="cuda:0")
+    X = _t(torch, X0)
+    U, Xl, Psi = torch.empty(steps, B, **kw), torch.empty(steps, 2, B, **kw), torch.empty(steps, 8, B, **kw)
+    d = [torch.empty(steps, B, **kw) for _ in range(3)]
+
+    def refused_diag(Xp, n_steps):
+        return lib.kmpc_rollout_diag(m.h, 0, Xp, m._p(rr), per, n_steps, 99, 102, 0.05, m._p(U), m._p(Xl), m._p(Psi), m._p(d[0]), m._p(d[1]),
+                                     m._p(d[2]), m._p(m.status), m._p(m.iters), m._stream())
+
+    def same_step():
+        u, ut = m.step(X, r), twin.step(Xt, r)
+        assert torch.equal(u, ut) and torch.equal(m.Useq, twin.Useq) and torch.equal(m.status, twin.status)
+        assert np.array_equal(m.state_dict()["blob"], twin.state_dict()["blob"])
+
+    assert refused_diag(None, steps) == -3
+    assert refused_diag(m._p(X), -1) == -3
+    Xt = _t(torch, X0)
+    Um, Xlm = m.rollout("duffing", X, r, steps, step0=99, switch_step=102, log=True)
+    Ut, Xlt = twin.rollout("duffing", Xt, r, steps, step0=99, switch_step=102, log=True)
+    assert torch.equal(Um, Ut) and torch.equal(Xlm, Xlt) and torch.equal(X, Xt) and torch.equal(m.status, twin.status)
+    same_step()
+    delta = torch.zeros(int(lib.kmpc_gram_elems(m.h)), **kw)
+    assert lib.kmpc_shared_solve_plant(m.h, m._p(delta), m._p(rr), m._p(m.U0), m._p(m.Useq), m._p(m.status), m._p(m.iters), 0, None, 0, 0.05,
+                                       m._stream()) == -3
+    same_step()
+
+
 # ------------------------------------------------------------------ consecutive calls: the wrapper leaves the handle alone
 @pytest.mark.parametrize("route", ["fused", "fused+term3", "per-step"])
 def test_consecutive_diagnostics_calls_equal_consecutive_plain_calls(torch_mod, KM, route):
