@@ -302,7 +302,15 @@ int kmpc_terminal_from_dare(kmpc_handle* h, const double* Q, double R, int maxit
  * roll-out this happens INSIDE the launch (a plug-in variant of the kernel, made by this call: kmpc_rollout_plugin_status); on the
  * per-step route as RLS launch, Riccati kernel, QP launch.  Until a trajectory's first refresh its block is the handle's current one
  * (kmpc_set_terminal_weight / kmpc_terminal_from_dare), else Qw I.  every = 0: off, the blocks stay what the last refresh left.
- * float64 handles, per-trajectory models (not the shared-model mode).                                                            */
+ * float64 handles, per-trajectory models (not the shared-model mode).
+ * The period is counted in control steps since this call armed the handle, through kmpc_step and kmpc_rollout calls alike: the steps
+ * whose count is a multiple of `every` refresh (the first step after arming does), however the steps are split into calls.  Every call
+ * with every > 0 -- re-arming included -- restarts the count.  A checkpoint does not carry the count: kmpc_state_import leaves the
+ * importing handle's count as it is, so a freshly armed handle refreshes at its FIRST step after the import and at every `every`-th after
+ * it, whatever the exporter's phase was; the steps in between use the blocks of the blob.  A blob that holds one block for the batch (or
+ * none) imported into an armed handle gives that block (or Qw I) to every trajectory.
+ * Delta-u handles are accepted: the Riccati iteration runs on the un-augmented [A B], and its q x q block Co P Co' is the terminal block
+ * of the output weight of the augmented condensed QP ([A B; 0 1], [B; 1], [Co 0]).                                                  */
 int kmpc_set_terminal_refresh(kmpc_handle* h, int every, const double* Q_host, double R, int maxiter, double eps);
 
 /* ---- state hand-over / checkpoint ------------------------------------------------------ */

@@ -1690,6 +1690,20 @@ struct Impl : kmpc_handle {
     }
     have_wterm = hd.have_wterm != 0; wterm_from_dare = hd.wterm_from_dare != 0; wterm_per_traj = hd.wterm_per_traj != 0;
     cfg.P0 = hd.P0; cfg.barQ0 = hd.barQ0;
+    if constexpr (sizeof(T) == 8) {
+      // terminal refresh armed: its launches read one block per trajectory (dWtB[B]) whatever the blob held.  A blob with one block
+      // for the batch (or none) gives that block (or Qw I) to every trajectory until its next refresh -- the copy above filled
+      // trajectory 0 alone and left the other B - 1 what they were before the import.
+      if (term_every > 0 && !(have_wterm && wterm_from_dare && wterm_per_traj)) {
+        std::vector<double> w0((size_t)q * q, 0.0);
+        if (have_wterm) HIPCHK(hipMemcpy(w0.data(), wterm_from_dare ? (const void*)dWtB : (const void*)dWt, sizeof(double) * w0.size(), hipMemcpyDeviceToHost));
+        { int rc = dare_buffers(B); if (rc) return rc; }
+        std::vector<double> wb((size_t)B * q * q);
+        for (int b = 0; b < B; ++b) std::copy(w0.begin(), w0.end(), wb.begin() + (size_t)b * q * q);
+        HIPCHK(hipMemcpy(dWtB, wb.data(), sizeof(double) * wb.size(), hipMemcpyHostToDevice));
+        have_wterm = true; wterm_from_dare = true; wterm_per_traj = true;
+      }
+    }
     // the host copy of a given P_N (kmpc_mpc_solve with another Q re-forms the block from it) and -- float32 handle with a float64
     // core -- the core's terminal weight follow the blob: the core only learns about a weight through set_terminal_weight, so a
     // checkpoint loaded into a fresh handle would otherwise run its fused roll-outs WITHOUT the terminal block, and one without a block
