@@ -35,7 +35,12 @@ enum { KMPC_F32 = 0, KMPC_F64 = 1 };
 enum {
   KMPC_LIFT_MLP = 0,        /* AutoEncoder.Encoder, duffing.py:17-29                      */
   KMPC_LIFT_RBF_PY = 1,     /* d^2 log(d + eps), vanderpol_RBF.py:20-23                   */
-  KMPC_LIFT_RBF_MATLAB = 2  /* r2 log(sqrt(r2)), NaN -> 0, rbf.m:24-29                    */
+  KMPC_LIFT_RBF_MATLAB = 2, /* r2 log(sqrt(r2)), NaN -> 0, rbf.m:24-29  ('thinplate')       */
+  /* the other kernels of rbf(X, C, type, eps, k): r2 = sum((x - c).^2) summed as in the thin plate above, eps = kmpc_config.rbf_eps */
+  KMPC_LIFT_RBF_GAUSS = 3,        /* exp(-eps^2 r2), rbf.m:31                             */
+  KMPC_LIFT_RBF_INVQUAD = 4,      /* 1 / (1 + eps^2 r2), rbf.m:33                         */
+  KMPC_LIFT_RBF_INVMULTQUAD = 5,  /* 1 / sqrt(1 + eps^2 r2), rbf.m:36                     */
+  KMPC_LIFT_RBF_POLYHARMONIC = 6  /* r2^(k/2) log(sqrt(r2)), NaN -> 0, rbf.m:38-39; k: kmpc_set_rbf_order */
 };
 enum {
   KMPC_OUT_CX = 0,   /* y = C x, C adapted by RLS (duffing.py:553, 943-953); q = n        */
@@ -84,7 +89,10 @@ typedef struct kmpc_config {
   double barQ0;        /* bar_Q init scale (100 duffing.py:946)                            */
   double Qw, Rw;       /* stage weights (100, 1e-4: duffing.py:580)                        */
   double lb, ub;       /* input box (+-2 duffing.py:636; +-6 vanderpol.py:542-544)         */
-  double rbf_eps;      /* 1e-4 (vanderpol_RBF.py:22)                                       */
+  double rbf_eps;      /* KMPC_LIFT_RBF_PY: the offset inside the logarithm, 1e-4 (vanderpol_RBF.py:22).
+                          KMPC_LIFT_RBF_GAUSS / INVQUAD / INVMULTQUAD: rbf.m's `eps`, the kernel width (MATLAB default 1,
+                          rbf.m:12-14); must be finite.  Unused for KMPC_LIFT_RBF_MATLAB and KMPC_LIFT_RBF_POLYHARMONIC,
+                          as in rbf.m                                                          */
   double umin, umax;   /* delta_u: absolute input range folded into the first increment's box
                           (A_cons, b_cons of Tank_System.m:182-188)                           */
 } kmpc_config;
@@ -105,6 +113,11 @@ int kmpc_set_encoder_layer(kmpc_handle* h, int layer, const double* W_host, cons
                            int rows, int cols);
 /* RBF centres cx (L x n)                                             vanderpol_RBF.py:44-46 */
 int kmpc_set_centres(kmpc_handle* h, const double* cx_host, int L, int n);
+/* the polyharmonic coefficient k of rbf(X, C, 'polyharmonic', eps, k): r2^(k/2) log(sqrt(r2))  rbf.m:15-17, 38
+ * Default 1.  k is an integer in 1..8: an even k is a product of k/2 factors r2, an odd k sqrt(r2) times that product (no pow).
+ * Takes effect for every later call of every route, like kmpc_set_centres.  Returns -3 on a handle of any other lift kind and
+ * for k outside 1..8.                                                                       */
+int kmpc_set_rbf_order(kmpc_handle* h, int k);
 /* model used until the first online update exists: Aloc_d, Bloc_d, Cloc_d = offline A, B, C
  * (duffing.py:811-813).  A (L x L), B (L), C (n x L; ignored for KMPC_OUT_LIFT); broadcast
  * to every trajectory.                                                                      */

@@ -25,6 +25,7 @@ struct kmpc_handle {
   }
   virtual int set_encoder_layer(int layer, const double* W, const double* b, int rows, int cols) = 0;
   virtual int set_centres(const double* cx, int L, int n) = 0;
+  virtual int set_rbf_order(int k) = 0;
   virtual int set_model(const double* A, const double* B, const double* C) = 0;
   virtual int set_terminal_weight(const double* PN) = 0;
   virtual int terminal_from_dare(const double* Qh, double R, int maxiter, double eps, int per_traj, double* PN_out,
@@ -211,7 +212,9 @@ struct Impl : kmpc_handle {
   // asks for the object of variant[term][diag] (process table, kernel cache, else hipcc); false: this configuration has no such object
   bool load_variant(bool term, bool diag) {
     RolloutVariant& v = variant[term][diag];
-    if (!rollout_plugin_key(n, L, N, q, cfg.lift_kind != KMPC_LIFT_MLP, enc.Lp, enc.KS, enc.Hp, B, sizeof(T) == 4, &v.plugin.key, term, diag)) return false;
+    if (!rollout_plugin_key(n, L, N, q, cfg.lift_kind != KMPC_LIFT_MLP, enc.Lp, enc.KS, enc.Hp, B, sizeof(T) == 4, &v.plugin.key, term, diag,
+                            cfg.lift_kind >= KMPC_LIFT_RBF_GAUSS))
+      return false;
     v.plugin.fn = rollout_plugin_get(v.plugin.key, diag ? &diag_msg() : &v.msg);
     v.state = v.plugin.fn ? 1 : -1;
     return true;
@@ -233,6 +236,12 @@ struct Impl : kmpc_handle {
     *dbo = nullptr, *dcx = nullptr, *dTmp = nullptr;
   std::vector<bool> layer_set;
   bool centres_set = false;
+  int rbf_k = 1;  // polyharmonic coefficient (rbf.m:15-17), kmpc_set_rbf_order
+  // what the lift kernels get in LiftArgs / RolloutArgs::rbf_matlab: 0 / 1 the thin plates, else the kind with k in bits 8-15 (plant_device.h)
+  int rbf_code() const {
+    if (cfg.lift_kind <= KMPC_LIFT_RBF_MATLAB) return cfg.lift_kind == KMPC_LIFT_RBF_MATLAB ? 1 : 0;
+    return cfg.lift_kind | (rbf_k << 8);
+  }
   // profiling
   bool prof = false;
   std::vector<hipEvent_t> ev;  // triples
@@ -245,6 +254,9 @@ struct Impl : kmpc_handle {
     q = (c.output_kind == KMPC_OUT_LIFT) ? L : (c.out_rows > 0 ? c.out_rows : n);
     if (c.output_kind != KMPC_OUT_LIFT && (c.out_row0 < 0 || c.out_row0 + q > n)) FAIL(-2, "out_row0/out_rows outside C");
     if (c.delta_u && !(c.umax > c.umin)) FAIL(-2, "delta_u needs umin < umax");
+    if (c.lift_kind < KMPC_LIFT_MLP || c.lift_kind > KMPC_LIFT_RBF_POLYHARMONIC) FAIL(-2, "lift_kind must be one of KMPC_LIFT_* (0..6)");
+    if (c.lift_kind >= KMPC_LIFT_RBF_GAUSS && c.lift_kind <= KMPC_LIFT_RBF_INVMULTQUAD && !std::isfinite(c.rbf_eps))
+      FAIL(-2, "rbf_eps (the kernel width of rbf.m) must be finite for the gauss, invquad and invmultquad lifts");
     if (m != 1) FAIL(-2, "m must be 1 (the reference takes B_hat = K[:, Nlift], duffing.py:170-171)");
     if (n < 1 || n > 4) FAIL(-2, "n must be in 1..4");
     if (L < 1 || L > 64) FAIL(-2, "L must be in 1..64");
@@ -518,6 +530,14 @@ struct Impl : kmpc_handle {
     if (rc) return rc;
     if (core && (rc = core->set_centres(cx, L_, n_))) { err = core->err; return rc; }
     centres_set = true;
+    return 0;
+  }
+  // the polyharmonic coefficient k of rbf.m:38, for every later call of every route (it travels with the launch arguments)
+  int set_rbf_order(int k) override {
+    if (cfg.lift_kind != KMPC_LIFT_RBF_POLYHARMONIC) FAIL(-3, "handle was not created with KMPC_LIFT_RBF_POLYHARMONIC");
+    if (k < 1 || k > 8) FAIL(-3, "the polyharmonic coefficient k must be an integer in 1..8");
+    if (core) { const int rc = core->set_rbf_order(k); if (rc) { err = core->err; return rc; } }
+    rbf_k = k;
     return 0;
   }
 
@@ -862,7 +882,7 @@ struct Impl : kmpc_handle {
       a.Whp[0] = dWhp[0]; a.Whp[1] = dWhp[1] ? dWhp[1] : dWhp[0]; a.Wop = dWop; a.KSp = enc.KS;
       HIPCHK(launch_lift_mlp<T>(a, s));
     } else {
-      a.cx = dcx; a.eps = (T)cfg.rbf_eps; a.rbf_matlab = cfg.lift_kind == KMPC_LIFT_RBF_MATLAB;
+      a.cx = dcx; a.eps = (T)cfg.rbf_eps; a.rbf_matlab = rbf_code();
       HIPCHK(launch_lift_rbf<T>(a, s));
     }
     return 0;
@@ -1196,7 +1216,7 @@ struct Impl : kmpc_handle {
       r.Wop = dWop; r.bo = dbo; r.Hp = enc.Hp; r.Lp = enc.Lp; r.KS = enc.KS; r.nhh = cfg.layers - 1;
     } else {
       r.lift_rbf = 1;
-      r.cx = dcx; r.eps = (T)cfg.rbf_eps; r.rbf_matlab = cfg.lift_kind == KMPC_LIFT_RBF_MATLAB ? 1 : 0;
+      r.cx = dcx; r.eps = (T)cfg.rbf_eps; r.rbf_matlab = rbf_code();
     }
     r.psi[0] = dPsi[0]; r.psi[1] = dPsi[1]; r.cur = cur;
     r.steps = steps; r.step0 = step0; r.switch_step = switch_step;
@@ -1805,6 +1825,7 @@ struct StreamMarkAtExit {
 int kmpc_set_encoder(kmpc_handle* h, int layer, const double* W, const double* b, int rows, int cols) { NN(h); return h->set_encoder_layer(layer, W, b, rows, cols); }
 int kmpc_set_encoder_layer(kmpc_handle* h, int layer, const double* W, const double* b, int rows, int cols) { return kmpc_set_encoder(h, layer, W, b, rows, cols); }
 int kmpc_set_centres(kmpc_handle* h, const double* cx, int L, int n) { NN(h); return h->set_centres(cx, L, n); }
+int kmpc_set_rbf_order(kmpc_handle* h, int k) { NN(h); return h->set_rbf_order(k); }
 int kmpc_set_model(kmpc_handle* h, const double* A, const double* B, const double* C) { NN(h); return h->set_model(A, B, C); }
 int kmpc_set_terminal_weight(kmpc_handle* h, const double* PN) { NN(h); return h->set_terminal_weight(PN); }
 int kmpc_terminal_from_dare(kmpc_handle* h, const double* Q, double R, int maxiter, double eps, int per_trajectory,
@@ -1837,10 +1858,10 @@ int kmpc_rollout_is_fused(const kmpc_handle* h) { NN(h); return h->rollout_is_fu
 // want the kernel cache filled before the first kmpc_create (__graft_entry__.build(), an installer, the first rank of a node).
 static void put_text(char* text, int text_bytes, const std::string& t) { if (text && text_bytes > 0) snprintf(text, (size_t)text_bytes, "%s", t.c_str()); }
 // 1: made or found (*text: the object), -1: failed (*text: why), 0: the configuration has no object of this variant
-static int prebuild_variant(int n, int L, int N, int q, bool rbf, int hidden_eff, int batch, bool io32, bool term, bool diag, std::string* text) {
+static int prebuild_variant(int n, int L, int N, int q, bool rbf, int hidden_eff, int batch, bool io32, bool term, bool diag, std::string* text, bool rbf_kinds) {
   const EncoderShape e = encoder_shape(hidden_eff, 0, n, L);
   RolloutPluginKey k{};
-  if (!rollout_plugin_key(n, L, N, q, rbf, e.Lp, e.KS, e.Hp, batch, io32, &k, term, diag)) return 0;
+  if (!rollout_plugin_key(n, L, N, q, rbf, e.Lp, e.KS, e.Hp, batch, io32, &k, term, diag, rbf_kinds)) return 0;
   if (!rollout_plugin_get(k, text)) return -1;
   *text = rollout_plugin_describe(k);
   return 1;
@@ -1849,19 +1870,21 @@ int kmpc_rollout_plugin_prebuild(int n, int L, int N, int out_rows, int lift_kin
   auto say = [&](int code, const std::string& t) { put_text(text, text_bytes, t); return code; };
   const bool rbf = lift_kind != KMPC_LIFT_MLP, io32 = dtype == KMPC_F32;
   const int q = out_rows > 0 ? out_rows : n;
+  if (lift_kind < KMPC_LIFT_MLP || lift_kind > KMPC_LIFT_RBF_POLYHARMONIC) return say(-3, "lift_kind must be one of KMPC_LIFT_* (0..6)");  // (as kmpc_create)
   if (n != 2 || L < 1 || N < 1 || batch < 1 || (!rbf && (hidden_eff < 1 || hidden_eff > 128)) || (dtype != KMPC_F32 && dtype != KMPC_F64)) return say(-3, "bad arguments");
   if (!(io32 ? rollout_io32_available(n, L, N, q, rbf) : rollout_fused_available<double>(n, L, N, q, 64, rbf))) return say(2, "no fused roll-out for this configuration");
   std::string t;
-  const int rc = prebuild_variant(n, L, N, q, rbf, hidden_eff, batch, io32, false, false, &t);
+  const int rc = prebuild_variant(n, L, N, q, rbf, hidden_eff, batch, io32, false, false, &t, lift_kind >= KMPC_LIFT_RBF_GAUSS);
   return rc == 0 ? say(0, "built-in instantiation of libkoopmpc.so") : say(rc, t);
 }
 int kmpc_rollout_diag_plugin_prebuild(int n, int L, int N, int out_rows, int lift_kind, int hidden_eff, int batch, int with_term, char* text, int text_bytes) {
   auto say = [&](int code, const std::string& t) { put_text(text, text_bytes, t); return code; };
   const bool rbf = lift_kind != KMPC_LIFT_MLP;
   const int q = out_rows > 0 ? out_rows : n;
+  if (lift_kind < KMPC_LIFT_MLP || lift_kind > KMPC_LIFT_RBF_POLYHARMONIC) return say(-3, "lift_kind must be one of KMPC_LIFT_* (0..6)");  // (as kmpc_create)
   if (n != 2 || L < 1 || N < 1 || batch < 1 || (!rbf && (hidden_eff < 1 || hidden_eff > 128))) return say(-3, "bad arguments");
   std::string t;
-  const int rc = rollout_fused_available<double>(n, L, N, q, 64, rbf) ? prebuild_variant(n, L, N, q, rbf, hidden_eff, batch, false, with_term != 0, true, &t) : 0;
+  const int rc = rollout_fused_available<double>(n, L, N, q, 64, rbf) ? prebuild_variant(n, L, N, q, rbf, hidden_eff, batch, false, with_term != 0, true, &t, lift_kind >= KMPC_LIFT_RBF_GAUSS) : 0;
   return rc == 0 ? say(2, "no fused diagnostics variant for this configuration (per-step launches)") : say(rc, t);
 }
 int kmpc_rollout_plugin_status(const kmpc_handle* h, char* text, int text_bytes) {

@@ -100,6 +100,8 @@ template <typename T> struct LiftArgs {
   // k-steps: a fragment is ONE coalesced 512-byte wave load (the row-major form costs 16 segments of 32 bytes per load)
   const T* Whp[2]; const T* Wop; int KSp;
   // RBF
+  // rbf_matlab: 0 / 1 the two thin plates; the other kinds of rbf.m: the lift kind (3..6) in bits 0-7 and the polyharmonic k in
+  // bits 8-15 (plant_device.h kmpc_rbf_kind_of_r2), with rbf.m's kernel width in eps
   const T* cx; T eps; int rbf_matlab;
 };
 
@@ -114,7 +116,7 @@ template <typename T> struct RolloutArgs {
   const T* Whp[2]; const T* bh[2];
   const T* Wop; const T* bo;
   int Hp, Lp, KS, nhh;
-  const T* cx; T eps; int rbf_matlab;
+  const T* cx; T eps; int rbf_matlab;  // (as LiftArgs: kind and k of rbf.m's other kernels ride in rbf_matlab, no layout change; ks = -2 objects only)
   T* psi[2];                // [B][L] ping-pong: psi[cur] receives the lift of the first step
   int cur;
   int steps, step0, switch_step, have_prev, rls_fresh;
@@ -207,7 +209,8 @@ template <typename T> hipError_t launch_step(const StepArgs<T>& a, int threads, 
 template <typename T> bool rollout_fused_available(int n, int L, int N, int q, int threads, bool rbf);
 void set_rollout_workgroup(int trajectories);  // 0 = automatic, else 4 / 8 / 16 (process-wide)
 // ---- roll-out plug-ins (rollout_plugin.hip, rollout_jit.hip): the fused roll-out of a dimension set without a built-in instantiation
-// nw: trajectories per workgroup; ks: -1 RBF lift, 25 / 0 MLP lift (compile-time / run-time width); term: with the per-step terminal refresh;
+// nw: trajectories per workgroup; ks: -1 thin-plate RBF lift, -2 the RBF lift of rbf.m's other kinds (gauss, invquad, invmultquad,
+// polyharmonic: one object for the four, the kind is a launch argument), 25 / 0 MLP lift (compile-time / run-time width); term: with the per-step terminal refresh;
 // diag: with the diagnostics logs (RolloutArgs::diag)
 struct RolloutPluginKey { int L, N, q, nw, ks, io32, term, diag; };
 typedef hipError_t (*rollout_plugin_fn)(const RolloutArgs<double>* a, int waves, hipStream_t s);
@@ -222,9 +225,9 @@ template <typename T> hipError_t launch_rollout_fused(const RolloutArgs<T>& a, h
 bool rollout_builtin(int L, int N, int q, bool io32);  // libkoopmpc.so itself holds the instantiations of this set
 // the plug-in a launch of this configuration needs; false: none (built-in set, or the set does not fit the fused kernel at all)
 // (term: the variant with the per-step terminal refresh -- always a plug-in, also for the built-in sets; diag: the variant with the
-//  diagnostics logs -- likewise, float64 register-state sets only)
+//  diagnostics logs -- likewise, float64 register-state sets only; rbf_kinds: the RBF lift of rbf.m's other kinds -- likewise always a plug-in)
 bool rollout_plugin_key(int n, int L, int N, int q, bool rbf, int Lp, int KS, int Hp, int B, bool io32, RolloutPluginKey* out, bool term = false,
-                        bool diag = false);
+                        bool diag = false, bool rbf_kinds = false);
 // the MLP encoder as the kernels see it: effective hidden width (lift_offset = 2 carries x on 2 n more units), its padding, the padded
 // output rows and the MFMA k-steps of 4 over the hidden width
 struct EncoderShape { int hid, Hp, Lp, KS; };

@@ -4,6 +4,7 @@
 //                Revise_2/Encoder_Duffing.m:3-6, Encoder_Tank.m:3-5 (two hidden layers)
 //   RBF          psi_j = d_j^2 log(d_j + eps)                          vanderpol_RBF.py:20-23
 //                psi_j = r2 log(sqrt(r2)), NaN -> 0                    rbf.m:24-29
+//                gauss, invquad, invmultquad, polyharmonic of r2        rbf.m:30-39 (plant_device.h)
 //
 // MLP mapping: the batch is the GEMM N dimension.  A workgroup of four waves owns a tile of
 // 16 trajectories; the hidden rows (M) are split over the four waves, each wave keeps ITS
@@ -394,11 +395,19 @@ template <typename T> __global__ __launch_bounds__(256) void lift_rbf_kernel(con
       T v;
       if constexpr (std::is_same<T, double>::value) {
         if (n == 2) {  // (the fused roll-out's function: bit for bit its observables)
-          a.Psi[(size_t)j * a.ps_l + (size_t)b * a.ps_b] = kmpc_rbf_psi2(x[0], x[1], scx[j * 2], scx[j * 2 + 1], a.eps, a.rbf_matlab);
+          a.Psi[(size_t)j * a.ps_l + (size_t)b * a.ps_b] = a.rbf_matlab > 1 ? kmpc_rbf_kind2(x[0], x[1], scx[j * 2], scx[j * 2 + 1], a.eps, a.rbf_matlab)
+                                                                           : kmpc_rbf_psi2(x[0], x[1], scx[j * 2], scx[j * 2 + 1], a.eps, a.rbf_matlab);
           continue;
         }
       }
-      if (a.rbf_matlab) {
+      if (a.rbf_matlab > 1) {  // gauss, invquad, invmultquad, polyharmonic (rbf.m:30-39): kind and k in rbf_matlab, the width in eps
+        T r2 = T(0);
+        for (int i = 0; i < n; ++i) {
+          const T d = x[i] - scx[j * n + i];
+          r2 += d * d;
+        }
+        v = kmpc_rbf_kind_of_r2<T>(r2, a.eps, a.rbf_matlab);
+      } else if (a.rbf_matlab) {
         T r2 = T(0);
         for (int i = 0; i < n; ++i) {
           const T d = x[i] - scx[j * n + i];

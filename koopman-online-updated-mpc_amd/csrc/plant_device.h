@@ -107,4 +107,40 @@ static __device__ __attribute__((noinline)) double kmpc_rbf_psi2(double x0, doub
   return d * d * kmpc_logT<double>(d + eps);
 }
 
+// ---------------------------------------------------------------------------------------
+// The other four kernels of rbf.m's dictionary (rbf.m:30-39) as functions of r2 = sum((x - c).^2), eps = rbf.m's kernel width.
+// `code`: the lift kind in bits 0-7 (KMPC_LIFT_RBF_GAUSS = 3 .. KMPC_LIFT_RBF_POLYHARMONIC = 6, koopmpc.h), the polyharmonic
+// coefficient k = 1..8 in bits 8-15 -- what LiftArgs / RolloutArgs carry in `rbf_matlab` for these kinds (0 / 1 stay the two thin
+// plates).  The library exp, a true sqrt followed by a division; r2^(k/2) is a product of k / 2 factors r2, times sqrt(r2) for an
+// odd k (no pow, no exp(log)); the polyharmonic is 0 wherever r2 > 0 is false, as the MATLAB thin plate (NaN -> 0, rbf.m:39).
+// ---------------------------------------------------------------------------------------
+constexpr int RBF_CODE_GAUSS = 3, RBF_CODE_INVQUAD = 4, RBF_CODE_INVMULTQUAD = 5, RBF_CODE_POLYHARMONIC = 6;
+template <typename T> __device__ __forceinline__ T kmpc_rbf_kind_of_r2(T r2, T eps, int code) {
+  const int kind = code & 255;
+  if (kind == RBF_CODE_POLYHARMONIC) {
+    const int k = (code >> 8) & 255;
+    const T r = sqrt(r2);
+    T pw = (k & 1) ? r : T(1);
+    for (int i = 0; i < (k >> 1); ++i) pw *= r2;
+    return r2 > T(0) ? pw * kmpc_logT<T>(r) : T(0);
+  }
+  const T s = (eps * eps) * r2;
+  if (kind == RBF_CODE_GAUSS) return exp(-s);                // rbf.m:31
+  if (kind == RBF_CODE_INVQUAD) return T(1) / (T(1) + s);    // rbf.m:33
+  return T(1) / sqrt(T(1) + s);                              // rbf.m:36
+}
+// One observable of these kinds of a TWO-state plant in float64: the second function beside kmpc_rbf_psi2, for the same two reasons --
+// exp's and the logarithm's coefficients are not the step loop's registers, and the stand-alone lift and the fused roll-out run the SAME
+// machine code (Psi_log of a fused launch equals kmpc_lift of the same states bit for bit).  r2 is summed in the order of the MATLAB
+// thin-plate form above.  `code` must be wave-uniform.
+static __device__ __attribute__((noinline)) double kmpc_rbf_kind2(double x0, double x1, double c0, double c1, double eps, int code) {
+  const double d0 = x0 - c0, d1 = x1 - c1;
+  double r2 = 0.0;
+  r2 += d0 * d0;
+  r2 += d1 * d1;
+  // (`code` is the same in every lane of both callers but arrives in a vector register: back in a scalar one the selection below is
+  //  scalar branches, not execution masks held in scalar registers the callers' step loop needs)
+  return kmpc_rbf_kind_of_r2<double>(r2, eps, __builtin_amdgcn_readfirstlane(code));
+}
+
 }  // namespace kmpc

@@ -6,7 +6,7 @@
 // instantiation when a handle of that set is created: rollout_plugin.hip compiles THIS file with
 //
 //   hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -ffp-contract=fast -shared -DKMPC_JIT_L=.. -DKMPC_JIT_N=.. -DKMPC_JIT_Q=..
-//         -DKMPC_JIT_NW=4|8|16 -DKMPC_JIT_KS=-1|0|25 -DKMPC_JIT_IO32=0|1 -DKMPC_JIT_TERM=0|1 -DKMPC_JIT_DIAG=0|1  rollout_jit.hip -o <cache>/rollout_....so
+//         -DKMPC_JIT_NW=4|8|16 -DKMPC_JIT_KS=-2|-1|0|25 -DKMPC_JIT_IO32=0|1 -DKMPC_JIT_TERM=0|1 -DKMPC_JIT_DIAG=0|1  rollout_jit.hip -o <cache>/rollout_....so
 //
 // -- the compiler, the flags and the sources the built-in instantiations are made of --, keeps the shared object in the kernel cache
 // and loads it with dlopen.  The plug-in is self-contained (no symbol of the library): the library decides the workgroup size

@@ -237,7 +237,7 @@ __global__ __launch_bounds__((ro_max_threads<L_, N_, Q_, NW, KS_>())) void rollo
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   double* const smem = reinterpret_cast<double*>(smem_raw);
   constexpr int NC = NW == 4 ? 4 : 16;  // trajectory columns of the cooperative encoder
-  constexpr bool RBF = KS_ < 0;         // the lift kind is a compile-time property (KS_ = -1: thin-plate RBF, per wave)
+  constexpr bool RBF = KS_ < 0;         // the lift kind is a compile-time property (KS_ = -1: thin-plate RBF, per wave; -2: rbf.m's other kinds)
   const int tid0 = threadIdx.x;
   const int wave = __builtin_amdgcn_readfirstlane(tid0 >> 6);  // wave-uniform: trajectory index and LDS base stay scalar
   const int B = ra.s.B, n = ra.s.n, L = L_;
@@ -311,7 +311,11 @@ __global__ __launch_bounds__((ro_max_threads<L_, N_, Q_, NW, KS_>())) void rollo
       if (live && (lane & PSI_MASK) < L) {  // (n = 2: the plants of the roll-outs are two-state systems)
         const double x0 = io_ld<IOT>(a.X_rw, (size_t)b), x1 = io_ld<IOT>(a.X_rw, (size_t)B + b);
         const double* c = R.cx + (size_t)(lane & PSI_MASK) * n;
-        psi_i = kmpc_rbf_psi2(x0, x1, c[0], c[1], R.eps, R.rbf_matlab);  // (plant_device.h: the stand-alone lift's code)
+        // (plant_device.h: the stand-alone lift's code.  KS_ = -2: rbf.m's gauss / invquad / invmultquad / polyharmonic, kind and k in
+        //  rbf_matlab -- a compile-time property of the kernel, so that the thin-plate instantiations hold no second call: with a run-time
+        //  branch the (32, 40, 2) thin-plate kernel spilled more, profiles/rbf_kinds.txt)
+        if constexpr (KS_ == -2) psi_i = kmpc_rbf_kind2(x0, x1, c[0], c[1], R.eps, R.rbf_matlab);
+        else psi_i = kmpc_rbf_psi2(x0, x1, c[0], c[1], R.eps, R.rbf_matlab);
       }
     } else if constexpr (NW == 4) {  // (written for 4 or 8 columns; with 8 the 16x16x4 path below measures better: 89 vs 87 M steps/s)
       // Four or eight trajectories per workgroup (four / two workgroups per CU, which drift apart: a SIMD then holds
@@ -765,9 +769,11 @@ template <int L_, int N_, int Q_, typename IOT = double> static hipError_t launc
   // (the RBF lift never uses the template's tiling: one instantiation serves every workgroup size)
   const bool ks25 = !rbf && a.KS == 25 && a.Hp == 112;  // the reference's encoders: 100 hidden units
 #ifdef KMPC_ROLLOUT_JIT_TU
-  // a plug-in holds ONE kernel: KMPC_JIT_KS = -1 (RBF lift, any workgroup size), 25 or 0 (MLP lift) with KMPC_JIT_NW trajectories per workgroup
+  // a plug-in holds ONE kernel: KMPC_JIT_KS = -1 (thin-plate RBF lift, any workgroup size), -2 (rbf.m's other kinds, likewise), 25 or 0 (MLP lift)
+  // with KMPC_JIT_NW trajectories per workgroup
   constexpr int JKS = KMPC_JIT_KS, JNW = JKS < 0 ? 16 : KMPC_JIT_NW;
   if (rbf != (JKS < 0)) return hipErrorInvalidValue;
+  if (rbf && (a.rbf_matlab > 1) != (JKS == -2)) return hipErrorInvalidValue;  // (no object computes a thin plate for another kind, or the reverse)
   if (!rbf && (waves != JNW || ks25 != (JKS == 25))) return hipErrorInvalidValue;
   if ((a.term_every > 0) != (KMPC_JIT_TERM != 0)) return hipErrorInvalidValue;
   if (a.term_every > 0 && (!a.term_Q || !a.term_W || !a.term_scratch || a.term_scratch_stride < term_scratch_elems(L_) || !a.s.Wterm || !a.s.wterm_per_traj))
@@ -775,6 +781,7 @@ template <int L_, int N_, int Q_, typename IOT = double> static hipError_t launc
   if ((a.diag != 0) != (KMPC_JIT_DIAG != 0)) return hipErrorInvalidValue;
   return launch_rollout_nw<L_, N_, Q_, JNW, JKS, IOT, KMPC_JIT_TERM != 0, KMPC_JIT_DIAG != 0>(k, waves, lds, s);
 #else
+  if (rbf && a.rbf_matlab > 1) return hipErrorInvalidValue;  // (rbf.m's other kinds are always plug-ins: launch_rollout_fused)
   if (rbf) return launch_rollout_nw<L_, N_, Q_, 16, -1, IOT>(k, waves, lds, s);
   if constexpr (sizeof(IOT) == 4) {  // (float32 I/O: workgroups of sixteen and eight trajectories -- what rollout_waves picks for these sets)
     if (waves == 16) return ks25 ? launch_rollout_nw<L_, N_, Q_, 16, 25, IOT>(k, waves, lds, s) : launch_rollout_nw<L_, N_, Q_, 16, 0, IOT>(k, waves, lds, s);
@@ -855,8 +862,10 @@ template <typename T> bool rollout_fused_available(int n, int L, int N, int q, i
   const bool inst = rollout_builtin(L, N, q, false) || rollout_plugin_dims(n, L, N, q);
   return inst && rollout_waves(n, L, q, N, rbf, 64) > 0;  // (Lp <= 64)
 }
-bool rollout_plugin_key(int n, int L, int N, int q, bool rbf, int Lp, int KS, int Hp, int B, bool io32, RolloutPluginKey* out, bool term, bool diag) {
-  if ((!term && !diag && rollout_builtin(L, N, q, io32)) || !rollout_plugin_dims(n, L, N, q)) return false;
+bool rollout_plugin_key(int n, int L, int N, int q, bool rbf, int Lp, int KS, int Hp, int B, bool io32, RolloutPluginKey* out, bool term, bool diag,
+                        bool rbf_kinds) {
+  rbf_kinds = rbf_kinds && rbf;
+  if ((!term && !diag && !rbf_kinds && rollout_builtin(L, N, q, io32)) || !rollout_plugin_dims(n, L, N, q)) return false;
   if (term && io32) return false;  // (the refresh is a float64 feature, as kmpc_terminal_from_dare)
   if (diag && (io32 || !rollout_uses_image(n, L, N, q))) return false;  // (the diagnostics: float64 register-state sets)
   if (io32 && !step_v2_dims(L, N, q)) return false;
@@ -864,7 +873,7 @@ bool rollout_plugin_key(int n, int L, int N, int q, bool rbf, int Lp, int KS, in
   if (io32 && !rbf && waves == 4) waves = 8;  // (float32 panels: launch_rollout_impl)
   if (waves == 0) return false;
   out->L = L; out->N = N; out->q = q; out->io32 = io32 ? 1 : 0; out->term = term ? 1 : 0; out->diag = diag ? 1 : 0;
-  out->ks = rbf ? -1 : ((KS == 25 && Hp == 112) ? 25 : 0);
+  out->ks = rbf ? (rbf_kinds ? -2 : -1) : ((KS == 25 && Hp == 112) ? 25 : 0);
   out->nw = rbf ? 16 : waves;  // (the RBF kernel never uses the template's tiling: one object serves every workgroup size)
   return true;
 }
@@ -880,7 +889,7 @@ template <> hipError_t launch_rollout_fused<double>(const RolloutArgs<double>& a
   if (a.s.B <= 0 || a.steps <= 0) return hipSuccess;
   if (!a.lift_rbf && (a.Hp > 128 || (a.Hp & 15) || a.Lp > 64 || a.KS > 32 || a.nhh < 0 || a.nhh > 2 || a.s.n > 4))
     return hipErrorInvalidValue;
-  if (a.term_every > 0 || a.diag || !rollout_builtin(a.s.L, a.s.N, a.s.q, a.io_f32 != 0)) return launch_rollout_plugin(a, plugin, s);
+  if (a.term_every > 0 || a.diag || (a.lift_rbf && a.rbf_matlab > 1) || !rollout_builtin(a.s.L, a.s.N, a.s.q, a.io_f32 != 0)) return launch_rollout_plugin(a, plugin, s);
   if (a.io_f32) return launch_rollout_io32(a, s);
   using IOT = double;
   KMPC_ROLLOUT_SETS_F64(KMPC_SET_LAUNCH)

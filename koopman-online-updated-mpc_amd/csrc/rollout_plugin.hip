@@ -9,7 +9,7 @@
 //   1. the process's table of loaded plug-ins (a second thread asking for a key that is being made waits for it; other keys do not),
 //   2. the kernel cache on disk -- $KMPC_KERNEL_CACHE, <library directory>/kernel_cache (what __graft_entry__.build() pre-builds
 //      travels with the tree), $XDG_CACHE_HOME/koopmpc, ~/.cache/koopmpc, $TMPDIR/koopmpc-<uid> -- file
-//      rollout_L.._N.._q.._nw.._ks.._f64|f32[_term][_diag]_<hash>.so, the hash over the sources, the compiler flags and the compiler's --version, so
+//      rollout_L.._N.._q.._nw.._ks.._f64|f32[_term][_diag]_<hash>.so (ksm1: thin-plate RBF lift, ksm2: rbf.m's other kinds), the hash over the sources, the compiler flags and the compiler's --version, so
 //      that a changed header or a new ROCm never meets a stale object,
 //   3. hipcc on csrc/rollout_jit.hip (the sources ship next to the library) with the flags of the library's own build, 4-8 s per kernel,
 //      under a file lock (the ranks of a node build an object once; the lock file stays), written under a temporary name and renamed,

@@ -14,6 +14,7 @@ LIB_PATH = os.environ.get("KMPC_LIB") or os.path.join(os.path.dirname(_PKG_DIR),
 
 KMPC_F32, KMPC_F64 = 0, 1
 KMPC_LIFT_MLP, KMPC_LIFT_RBF_PY, KMPC_LIFT_RBF_MATLAB = 0, 1, 2
+KMPC_LIFT_RBF_GAUSS, KMPC_LIFT_RBF_INVQUAD, KMPC_LIFT_RBF_INVMULTQUAD, KMPC_LIFT_RBF_POLYHARMONIC = 3, 4, 5, 6  # rbf.m:30-39
 KMPC_OUT_CX, KMPC_OUT_LIFT = 0, 1
 KMPC_PLANT_DUFFING, KMPC_PLANT_VDP, KMPC_PLANT_TANK = 0, 1, 2
 KMPC_PLANT_RK4_MATLAB = 16
@@ -45,6 +46,7 @@ SIGNATURES = {
     "kmpc_set_encoder": (_I, [_VP, _I, _DP, _DP, _I, _I]),
     "kmpc_set_encoder_layer": (_I, [_VP, _I, _DP, _DP, _I, _I]),
     "kmpc_set_centres": (_I, [_VP, _DP, _I, _I]),
+    "kmpc_set_rbf_order": (_I, [_VP, _I]),
     "kmpc_set_model": (_I, [_VP, _DP, _DP, _DP]),
     "kmpc_set_terminal_weight": (_I, [_VP, _DP]),
     "kmpc_solve_dare": (_I, [_VP, _VP, _DP, _D, _I, _D, _I, _I, _VP, _VP, _VP, _VP]),

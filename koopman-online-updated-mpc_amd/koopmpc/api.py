@@ -83,12 +83,20 @@ class KoopmanMPC:
     ``lift_offset``: None (the raw encoder, as the Python scripts lift), "psi0" -> psi(x) - psi(0)
     (Koopman_update_Tracking_Lift.m:65), "x_psi0" -> [x; psi(x)] - [0; psi(0)] with L = n + the encoder's outputs
     (Koopman_update.m:67).
+    ``lift``: "mlp", the thin plates "rbf" (vanderpol_RBF.py:20-23) and "rbf_matlab" (rbf.m:26-29), or one of rbf.m's other kernels
+    (rbf.m:30-39): "rbf_gauss" exp(-eps^2 r2), "rbf_invquad" 1 / (1 + eps^2 r2), "rbf_invmultquad" 1 / sqrt(1 + eps^2 r2),
+    "rbf_polyharmonic" r2^(k/2) log(sqrt(r2)).  ``rbf_eps``: the offset inside the logarithm of "rbf" (None -> 1e-4), rbf.m's kernel
+    width `eps` for gauss / invquad / invmultquad (None -> 1, rbf.m:12-14).  ``rbf_k``: the polyharmonic coefficient, an integer in 1..8 (read for "rbf_polyharmonic" only, as rbf.m reads k).
     """
+
+    LIFT_KINDS = {"mlp": _ffi.KMPC_LIFT_MLP, "rbf": _ffi.KMPC_LIFT_RBF_PY, "rbf_matlab": _ffi.KMPC_LIFT_RBF_MATLAB,
+                  "rbf_gauss": _ffi.KMPC_LIFT_RBF_GAUSS, "rbf_invquad": _ffi.KMPC_LIFT_RBF_INVQUAD,
+                  "rbf_invmultquad": _ffi.KMPC_LIFT_RBF_INVMULTQUAD, "rbf_polyharmonic": _ffi.KMPC_LIFT_RBF_POLYHARMONIC}
 
     def __init__(self, n=2, L=8, N=10, batch=1, lift="mlp", weights=None, centres=None, hidden=100, layers=3,
                  output="Cx", dtype=torch.float64, lam=1.0, P0=1e4, barQ0=100.0, Qw=100.0, Rw=1e-4, lb=-2.0,
-                 ub=2.0, rbf_eps=1e-4, qp_max_iter=0, threads=0, device=None, delta_u=False, out_row0=0, out_rows=0,
-                 c_skip_first=False, umin=-8.0, umax=8.0, cold_start=False, lift_offset=None):
+                 ub=2.0, rbf_eps=None, qp_max_iter=0, threads=0, device=None, delta_u=False, out_row0=0, out_rows=0,
+                 c_skip_first=False, umin=-8.0, umax=8.0, cold_start=False, lift_offset=None, rbf_k=1):
         if not torch.cuda.is_available():
             raise RuntimeError("koopmpc needs a HIP device (MI355X); there is no CPU path")
         self.lib = _ffi.load()
@@ -100,7 +108,9 @@ class KoopmanMPC:
         self.n, self.L, self.N, self.B = int(n), int(L), int(N), int(batch)
         self.q = self.L if output == "lift" else (int(out_rows) if out_rows else self.n)
         self.output = output
-        lift_kind = {"mlp": _ffi.KMPC_LIFT_MLP, "rbf": _ffi.KMPC_LIFT_RBF_PY, "rbf_matlab": _ffi.KMPC_LIFT_RBF_MATLAB}[lift]
+        lift_kind = self.LIFT_KINDS[lift]
+        if rbf_eps is None:
+            rbf_eps = 1.0 if lift_kind >= _ffi.KMPC_LIFT_RBF_GAUSS else 1e-4
         cfg = _ffi.KmpcConfig(
             n=n, m=1, L=L, N=N, hidden=hidden, layers=layers, lift_kind=lift_kind,
             output_kind=_ffi.KMPC_OUT_LIFT if output == "lift" else _ffi.KMPC_OUT_CX,
@@ -114,6 +124,8 @@ class KoopmanMPC:
         rc = self.lib.kmpc_create(C.byref(cfg), C.byref(h))
         _ffi.check(self.lib, None, rc, "kmpc_create")
         self.h = h
+        if lift_kind == _ffi.KMPC_LIFT_RBF_POLYHARMONIC:  # (rbf.m reads k in the polyharmonic case only: ignored for every other lift, as rbf() does)
+            self.set_rbf_order(rbf_k)
         if weights is not None:
             self.set_encoder(weights)
         if centres is not None:
@@ -161,6 +173,12 @@ class KoopmanMPC:
     def set_centres(self, cx):
         cx = np.ascontiguousarray(cx, dtype=np.float64)
         self._chk(self.lib.kmpc_set_centres(self.h, _dptr(cx), cx.shape[0], cx.shape[1]), "kmpc_set_centres")
+
+    def set_rbf_order(self, k):
+        """The polyharmonic coefficient k of rbf(X, C, 'polyharmonic', eps, k) (rbf.m:15-17, 38): an integer in 1..8, for every later call."""
+        if int(k) != k:
+            raise ValueError("the polyharmonic coefficient k must be an integer in 1..8")
+        self._chk(self.lib.kmpc_set_rbf_order(self.h, int(k)), "kmpc_set_rbf_order")
 
     def set_model(self, A, B, Cm=None):
         """Aloc_d, Bloc_d, Cloc_d = A, B, C  (duffing.py:811-813): the model used until the first update."""
@@ -679,13 +697,35 @@ class AutoEncoder:
     __call__ = Encoder
 
 
-def rbf(X, cx, eps=1e-4, form="python", device=None):
-    """rbf(X, cx) of vanderpol_RBF.py:20-23 / duffing_RBF.py:20-23 (form="matlab": rbf.m:24-29): psi_j = d_j^2 log(d_j + eps).
+_RBF_TYPES = {"thinplate": "rbf_matlab", "gauss": "rbf_gauss", "invquad": "rbf_invquad", "invmultquad": "rbf_invmultquad",
+              "polyharmonic": "rbf_polyharmonic"}  # rbf.m:25-39 -> KoopmanMPC(lift=...)
+
+
+def _rbf_arguments(eps, form, type, k):
+    """(lift name, eps, k) of a module-level rbf() call.  Without `type`: the Python scripts' rbf(X, cx), eps (default 1e-4) the offset
+    inside the logarithm.  With `type`: rbf.m -- the name is lower-cased (rbf.m:11), eps defaults to 1 (rbf.m:12-14), k to 1."""
+    if type is None:
+        return ("rbf" if form == "python" else "rbf_matlab"), (1e-4 if eps is None else float(eps)), 1
+    lift = _RBF_TYPES.get(str(type).lower())
+    if lift is None:
+        raise ValueError("RBF type not recognize")  # (rbf.m:41, verbatim)
+    if lift != "rbf_polyharmonic":
+        k = 1  # (rbf.m reads k in the polyharmonic case only)
+    elif int(k) != k or not 1 <= int(k) <= 8:
+        raise ValueError("the polyharmonic coefficient k must be an integer in 1..8")
+    return lift, (1.0 if eps is None else float(eps)), int(k)
+
+
+def rbf(X, cx, eps=None, form="python", device=None, type=None, k=1):
+    """rbf(X, cx) of vanderpol_RBF.py:20-23 / duffing_RBF.py:20-23 (form="matlab": rbf.m:24-29): psi_j = d_j^2 log(d_j + eps), eps = 1e-4.
+    With `type` -- 'thinplate' (= form="matlab"), 'gauss', 'invquad', 'invmultquad', 'polyharmonic', in any letter case -- it is
+    rbf(X, C, type, eps, k) of rbf.m:10-44 with cx = C' : eps is then the kernel width (default 1), k the polyharmonic coefficient.
     X (n,) | (n, 1) | (n, B), cx (L, n) -> (L, 1) for a single state like the reference, else (L, B)."""
+    lift, eps, k = _rbf_arguments(eps, form, type, k)
     cx = np.ascontiguousarray(cx, dtype=np.float64)
     L, n = cx.shape
-    m = _handle(("rbf", L, n, form, float(eps), str(device)),
-                lambda: KoopmanMPC(n=n, L=L, N=2, batch=1, lift="rbf" if form == "python" else "rbf_matlab", centres=cx, rbf_eps=eps, device=device))
+    m = _handle(("rbf", L, n, lift, eps, k, str(device)),
+                lambda: KoopmanMPC(n=n, L=L, N=2, batch=1, lift=lift, centres=cx, rbf_eps=eps, rbf_k=k, device=device))
     return m.rbf(X, cx)
 
 

@@ -22,6 +22,10 @@ DEFAULT_SETS = [
     (2, 10, 10, 0, "mlp", 104, 64, "f64"),
     (2, 10, 10, 0, "mlp", 104, 4096, "f64"),
     (2, 10, 10, 0, "mlp", 100, 4096, "f64"),
+    # rbf.m's gauss / invquad / invmultquad / polyharmonic dictionaries at BASELINE cfg3's set and at the reference's (8, 10)
+    (2, 8, 30, 0, "rbf_gauss", 0, 4096, "f64"),
+    (2, 8, 30, 0, "rbf_gauss", 0, 4096, "f32"),  # (... behind float32 panels: a KMPC_F32 handle of that set)
+    (2, 8, 10, 0, "rbf_gauss", 0, 64, "f64"),
 ]
 # The diagnostics variants of the fused roll-out (kmpc_set_rollout_diagnostics; always plug-ins, float64), in the form of DEFAULT_SETS:
 # the dtype field reads "f64+diag", or "f64+term+diag" for the variant that also holds the terminal refresh.  The reference's set
@@ -31,14 +35,19 @@ DIAG_SETS = [
     (2, 8, 10, 0, "mlp", 100, 64, "f64+term+diag"),
     (2, 20, 20, 0, "mlp", 100, 4096, "f64+diag"),
     (2, 8, 30, 0, "rbf", 0, 4096, "f64+diag"),
+    (2, 8, 10, 0, "rbf_gauss", 0, 64, "f64+diag"),  # (rbf.m's other kinds at the reference's set)
 ]
-_KIND = {"mlp": _ffi.KMPC_LIFT_MLP, "rbf": _ffi.KMPC_LIFT_RBF_PY, "rbf_matlab": _ffi.KMPC_LIFT_RBF_MATLAB}
+_KIND = {"mlp": _ffi.KMPC_LIFT_MLP, "rbf": _ffi.KMPC_LIFT_RBF_PY, "rbf_matlab": _ffi.KMPC_LIFT_RBF_MATLAB,
+         # (rbf.m's other kernels: ONE object for the four -- ..._ksm2_... beside the thin plates' ..._ksm1_... --, always a plug-in,
+         #  also for the built-in dimension sets; which of the four, its width and k are launch arguments)
+         "rbf_gauss": _ffi.KMPC_LIFT_RBF_GAUSS, "rbf_invquad": _ffi.KMPC_LIFT_RBF_INVQUAD,
+         "rbf_invmultquad": _ffi.KMPC_LIFT_RBF_INVMULTQUAD, "rbf_polyharmonic": _ffi.KMPC_LIFT_RBF_POLYHARMONIC}
 
 
 def prebuild(sets=None, verbose=False):
     """Make (or find) the plug-ins of the given configurations; returns [(set, code, text)] with code as kmpc_rollout_plugin_status
     (a diagnostics set: 1 plug-in, 2 no fused variant -- per-step launches --, -1 failed).
-    NOTE: without `sets` this is DEFAULT_SETS followed by DIAG_SETS -- four more objects, 5-6 s of hipcc each on a cold cache.
+    NOTE: without `sets` this is DEFAULT_SETS followed by DIAG_SETS -- five more objects, 5-6 s of hipcc each on a cold cache.
     `__graft_entry__.build()` calls it this way, so that the diagnostics plug-ins of the reference's and the BASELINE sets travel with
     the tree and `prune` keeps them."""
     lib = _ffi.load()

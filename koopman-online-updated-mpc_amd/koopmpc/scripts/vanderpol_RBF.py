@@ -28,6 +28,10 @@ def main():
     ap.add_argument("--switch-step", type=int, default=None,
                     help="first step with the switched plant parameters (default: none for vdp as before, 102 for duffing: "
                          "duffing_RBF.py:505-506 switches after iteration 101)")
+    ap.add_argument("--rbf-type", default=None, choices=["thinplate", "gauss", "invquad", "invmultquad", "polyharmonic"],
+                    help="rbf.m's rbf_type (Koopman_update_Tracking_Lift.m:60-62, rbf.m:25-39); default: the thin plate of vanderpol_RBF.py:20-23")
+    ap.add_argument("--rbf-eps", type=float, default=None, help="rbf.m's kernel width eps of gauss / invquad / invmultquad (default 1)")
+    ap.add_argument("--rbf-k", type=int, default=1, help="rbf.m's polyharmonic coefficient k, 1..8")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     X, Y, U = offline_data(plant=vdp_rk4) if a.plant == "vdp" else offline_data()  # (data_generator.duffing_generate(), duffing_RBF.py:40)
@@ -38,7 +42,10 @@ def main():
     except Exception:  # no scikit-learn: data points as centres
         cx = X[:, np.random.RandomState(101).choice(X.shape[1], a.Nrbf, replace=False)].T.copy()
     B, N = a.batch, a.horizon
-    mpc = KoopmanMPC(n=2, L=a.Nrbf, N=N, batch=B, lift="rbf", centres=cx, lb=-a.bound, ub=a.bound, P0=1e5, barQ0=1e5)
+    lift = "rbf" if a.rbf_type is None else ("rbf_matlab" if a.rbf_type == "thinplate" else "rbf_" + a.rbf_type)
+    mpc = KoopmanMPC(n=2, L=a.Nrbf, N=N, batch=B, lift=lift, centres=cx, lb=-a.bound, ub=a.bound, P0=1e5, barQ0=1e5,
+                     rbf_eps=a.rbf_eps if lift in ("rbf_gauss", "rbf_invquad", "rbf_invmultquad") else None,
+                     rbf_k=a.rbf_k if lift == "rbf_polyharmonic" else 1)
     mpc.offline_fit(X, Y, U, ridge=1e-9, init_rls=True)       # offline fit (:78-103) + storage semantics (:434-438)
     r = np.concatenate([np.ones((1, N)), np.zeros((1, N))], axis=0)
     x0 = np.tile(np.array([[-2.0], [-2.0]]), (1, B)) if B == 1 else initial_states(B)
