@@ -75,46 +75,22 @@ __device__ __forceinline__ void halves_both_q(double a, double& lo, double& hi) 
   lo = __hiloint2double(rh[0], rl[0]);
   hi = __hiloint2double(rh[1], rl[1]);
 }
-// ac[l & 3] += M[l] * vec[l], l < N (vec as v0 / v1 of half_gather)
-template <int N_, int l = 0>
-__device__ __forceinline__ void rl_dot(double (&ac)[4], double v0, double v1, const double (&M)[N_]) {
-  if constexpr (l < N_) {
-    if constexpr (l < 16) fmac_rowbcast<l, l == 0>(ac[l & 3], v0, M[l]);
-    else fmac_rowbcast<l - 16, l == 16>(ac[l & 3], v1, M[l]);
-    rl_dot<N_, l + 1>(ac, v0, v1, M);
-  }
-}
-template <int N_, int l = 0>
-__device__ __forceinline__ void rl_upd(double (&M)[N_], double v0, double v1, double coef) {
-  if constexpr (l < N_) {
-    if constexpr (l < 16) fmac_rowbcast<l, l == 0>(M[l], v0, coef);
-    else fmac_rowbcast<l - 16, l == 16>(M[l], v1, coef);
-    rl_upd<N_, l + 1>(M, v0, v1, coef);
-  }
+// M[l] += vec[l] * coef, l < N (vec as v0 / v1 of half_gather)
+template <int N_> __device__ __forceinline__ void rl_upd(double (&M)[N_], double v0, double v1, double coef) {
+  row_upd<N_, -1>(M, v0, v1, coef);
 }
 // y = M v for the rows in this lane's half (v: one element per lane of the half)
-template <int N_, int l = 0>
-__device__ __forceinline__ void rl_dot1(double& ac, double v0, double v1, const double (&M)[N_]) {
-  if constexpr (l < N_) {
-    if constexpr (l < 16) fmac_rowbcast<l, l == 0>(ac, v0, M[l]);
-    else fmac_rowbcast<l - 16, l == 16>(ac, v1, M[l]);
-    rl_dot1<N_, l + 1>(ac, v0, v1, M);
-  }
-}
 template <int N_> __device__ __forceinline__ double rl_matvec(const double (&M)[N_], double v) {
   double v0, v1;
   half_gather(v, v0, v1);
-  if constexpr (N_ > 0) {
-    // (long horizons run sixteen trajectories per CU on a saturated vector pipe: ONE chain of multiply-adds -- the other waves cover
-    //  its latency -- instead of four partial sums with their four register clears and three adds)
-    double ac = 0.0;
-    rl_dot1<N_>(ac, v0, v1, M);
-    return ac;
-  } else {
-    double ac[4] = {0.0, 0.0, 0.0, 0.0};
-    rl_dot<N_>(ac, v0, v1, M);
-    return (ac[0] + ac[1]) + (ac[2] + ac[3]);
-  }
+  // (sixteen trajectories per CU on a saturated vector pipe: ONE chain of multiply-adds -- the other waves cover its latency -- instead
+  //  of four partial sums with their four register clears and three adds; one asm statement, step_body.h row_dot)
+  // The block form from N = 17 on.  At the reference's horizon N = 10 it cost the roll-out plug-in of the MATLAB twin (generic encoder)
+  // its register allocation -- 111 instead of 50 spilled vector registers, in the encoder's weight fetches, not here -- and 23 % of the
+  // window, measured; the statement form is the same code as before there (profiles/dpp_blocks.txt).
+  double ac = 0.0;
+  row_dot<N_, (N_ > 16)>(ac, v0, v1, M);
+  return ac;
 }
 
 // Symmetric sweep of the tableau (lanes 0-31; lanes 32-63 hold H and must not change: their coefficient is zero) on variable K.

@@ -201,6 +201,98 @@ __device__ __forceinline__ void fmac_rowbcast(double& acc, double vec, double co
     asm volatile("v_fmac_f64_dpp %0, %1, %2 row_newbcast:%3 row_mask:0xf bank_mask:0xf"
                  : "+v"(acc) : "v"(vec), "v"(coef), "n"(LANE));
 }
+// A whole single-chain row product as ONE asm statement.  Between two asm statements of which the second reads a register the first
+// wrote (the tied accumulator of a chain) the compiler pads a wait state: it has to assume that an opaque statement forwards its
+// destination the slow way.  Statement by statement that was an s_nop in front of every multiply-add of a chain but the first (544 of the
+// 757 s_nop of the cfg2 roll-out kernel, 4 cycles of the wave's own instruction stream each); the hardware needs none, a chain of v_fmac_f64 runs
+// back to back.  The only hazard of the product is the one fmac_rowbcast pads: a fresh VALU write of the DPP source, `s_nop 1` in front.
+// The column count is a template parameter, so the text is built at compile time (asm with a constant-expression string: clang >= 21).
+struct RowAsm {
+  char s[2048];
+  int n;
+  constexpr const char* data() const { return s; }
+  constexpr size_t size() const { return (size_t)n; }
+};
+// ac (%0) += R[l] (%3 + l - L0) * vec[l], l = L0 .. L1-1; vec[l] = lane l of v0 (%1, l < 16) or lane l - 16 of v1 (%2)
+template <int L0, int L1, bool PAD> constexpr RowAsm row_dot_text() {
+  RowAsm t{};
+  auto put = [&t](const char* p) { while (*p) t.s[t.n++] = *p++; };
+  auto num = [&t](int v) { if (v >= 10) t.s[t.n++] = (char)('0' + v / 10); t.s[t.n++] = (char)('0' + v % 10); };
+  if (PAD) put("s_nop 1\n\t");
+  for (int l = L0; l < L1; ++l) {
+    put("v_fmac_f64_dpp %0, %"); num(l < 16 ? 1 : 2); put(", %"); num(3 + l - L0);
+    put(" row_newbcast:"); num(l & 15); put(" row_mask:0xf bank_mask:0xf");
+    if (l + 1 < L1) put("\n\t");
+  }
+  return t;
+}
+// (an asm statement takes 30 operands: the accumulator counts twice, v0, v1, 26 columns.  The operand lists come in steps of four
+//  columns: the slots behind the last column repeat column L0 -- the same value, no register of their own -- and the text does not name them)
+template <int L0, int L1, bool PAD, int NCOL>
+__device__ __forceinline__ void row_dot_block(double& ac, double v0, double v1, const double (&R)[NCOL]) {
+  static_assert(L0 >= 0 && L1 > L0 && L1 - L0 <= 26 && L1 <= NCOL && L1 <= 32, "row_dot_block: columns");
+#define KMPC_RC(i) "v"(R[L0 + (i) < L1 ? L0 + (i) : L0])
+#define KMPC_RC4(i) KMPC_RC(i), KMPC_RC(i + 1), KMPC_RC(i + 2), KMPC_RC(i + 3)
+#define KMPC_DOT(...) asm volatile((row_dot_text<L0, L1, PAD>()) : "+v"(ac) : "v"(v0), "v"(v1), __VA_ARGS__)
+  constexpr int K = L1 - L0;
+  if constexpr (K <= 4) KMPC_DOT(KMPC_RC4(0));
+  else if constexpr (K <= 8) KMPC_DOT(KMPC_RC4(0), KMPC_RC4(4));
+  else if constexpr (K <= 12) KMPC_DOT(KMPC_RC4(0), KMPC_RC4(4), KMPC_RC4(8));
+  else if constexpr (K <= 16) KMPC_DOT(KMPC_RC4(0), KMPC_RC4(4), KMPC_RC4(8), KMPC_RC4(12));
+  else if constexpr (K <= 20) KMPC_DOT(KMPC_RC4(0), KMPC_RC4(4), KMPC_RC4(8), KMPC_RC4(12), KMPC_RC4(16));
+  else if constexpr (K <= 24) KMPC_DOT(KMPC_RC4(0), KMPC_RC4(4), KMPC_RC4(8), KMPC_RC4(12), KMPC_RC4(16), KMPC_RC4(20));
+  else KMPC_DOT(KMPC_RC4(0), KMPC_RC4(4), KMPC_RC4(8), KMPC_RC4(12), KMPC_RC4(16), KMPC_RC4(20), KMPC_RC(24), KMPC_RC(25));
+#undef KMPC_DOT
+#undef KMPC_RC4
+#undef KMPC_RC
+}
+// the same product statement by statement (the form before the blocks: one pad per link of the chain)
+template <int CNT, int l = 0, int NCOL>
+__device__ __forceinline__ void row_dot_stmts(double& ac, double v0, double v1, const double (&R)[NCOL]) {
+  if constexpr (l < CNT) {
+    if constexpr (l < 16) fmac_rowbcast<l, l == 0>(ac, v0, R[l]);
+    else fmac_rowbcast<l - 16, l == 16>(ac, v1, R[l]);
+    row_dot_stmts<CNT, l + 1>(ac, v0, v1, R);
+  }
+}
+// ac += R[l] * vec[l], l < CNT: ONE chain of multiply-adds, one block up to 26 columns, else two (v1 was written before the first block:
+// sixteen instructions ahead of its first reader).  BLK = false: as statements (qp_rl.h rl_matvec says where and why)
+template <int CNT, bool BLK = true, int NCOL>
+__device__ __forceinline__ void row_dot(double& ac, double v0, double v1, const double (&R)[NCOL]) {
+  if constexpr (!BLK) {
+    row_dot_stmts<CNT>(ac, v0, v1, R);
+  } else if constexpr (CNT <= 26) {
+    row_dot_block<0, CNT, true>(ac, v0, v1, R);
+  } else {
+    row_dot_block<0, 16, true>(ac, v0, v1, R);
+    row_dot_block<16, CNT, false>(ac, v0, v1, R);
+  }
+}
+// R[l] += vec[l] * coef for l < CNT (coef is the lane's own); column LOWCOL only in the 16-lane rows 0 and 1 (lanes 0-31; -1: none).
+// Every column is an accumulator of its own: no statement reads what the one before wrote and the compiler pads nothing between them,
+// so the statements stay single.  (As blocks of 13 columns -- an accumulator counts twice towards the 30 operands of a statement --
+// every accumulator of a block has to sit in a register at once: the four-wave roll-out kernels, which spill, then spill 100 instead of
+// 85 registers, and the sixteen-wave kernels gain nothing.)  v1 is made an operand in front of column 0, whose `s_nop 1` therefore
+// covers both vectors: column 16 needs no pad of its own.
+template <int LANE, bool NOP, bool LOWHALF>
+__device__ __forceinline__ void fmac_rowbcast_m(double& acc, double vec, double coef) {
+  if constexpr (LOWHALF) {
+    if constexpr (NOP)
+      asm volatile("s_nop 1\n\tv_fmac_f64_dpp %0, %1, %2 row_newbcast:%3 row_mask:0x3 bank_mask:0xf" : "+v"(acc) : "v"(vec), "v"(coef), "n"(LANE));
+    else
+      asm volatile("v_fmac_f64_dpp %0, %1, %2 row_newbcast:%3 row_mask:0x3 bank_mask:0xf" : "+v"(acc) : "v"(vec), "v"(coef), "n"(LANE));
+  } else {
+    fmac_rowbcast<LANE, NOP>(acc, vec, coef);
+  }
+}
+template <int CNT, int LOWCOL, int l = 0, int NCOL>
+__device__ __forceinline__ void row_upd(double (&R)[NCOL], double v0, double v1, double coef) {
+  if constexpr (l < CNT) {
+    if constexpr (l == 0) asm volatile("" : : "v"(v1));
+    fmac_rowbcast_m<(l & 15), l == 0, l == LOWCOL>(R[l], l < 16 ? v0 : v1, coef);
+    row_upd<CNT, LOWCOL, l + 1>(R, v0, v1, coef);
+  }
+}
 // acc[l & 3] += row[l] * vec[l], vec[l] = lane l of v0 (l < 16) or lane l-16 of v1, within the reader's row
 template <int L_, int l = 0>
 __device__ __forceinline__ void chain_dot(double (&ac)[4], double v0, double v1, const double (&row)[L_]) {

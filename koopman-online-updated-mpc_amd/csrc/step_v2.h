@@ -53,59 +53,17 @@ static constexpr size_t v2_lds_elems(int L, int q, int N) { return ((size_t)v2_r
 // ---------------------------------------------------------------------------------------
 // row products on DPP
 // ---------------------------------------------------------------------------------------
-template <int LANE, bool NOP, bool LOWHALF>
-__device__ __forceinline__ void fmac_rowbcast_m(double& acc, double vec, double coef) {
-  // LOWHALF: only the 16-lane rows 0 and 1 (lanes 0-31) take part (row_mask 0x3)
-  if constexpr (LOWHALF) {
-    if constexpr (NOP)
-      asm volatile("s_nop 1\n\tv_fmac_f64_dpp %0, %1, %2 row_newbcast:%3 row_mask:0x3 bank_mask:0xf" : "+v"(acc) : "v"(vec), "v"(coef), "n"(LANE));
-    else
-      asm volatile("v_fmac_f64_dpp %0, %1, %2 row_newbcast:%3 row_mask:0x3 bank_mask:0xf" : "+v"(acc) : "v"(vec), "v"(coef), "n"(LANE));
-  } else {
-    fmac_rowbcast<LANE, NOP>(acc, vec, coef);
-  }
-}
-// a2[l & 3] += R2[l] * vec[l], a1[l & 3] += R1[l] * vec[l], l < CNT; vec[l] = lane l of v0 (l < 16) or lane l - 16 of v1 of the
-// reader's 16-lane row.  The two layers alternate: eight independent chains.
-template <int CNT, int NCOL, int l = 0>
-__device__ __forceinline__ void rowdot2(double (&a2)[4], double (&a1)[4], double v0, double v1, const double (&R2)[NCOL], const double (&R1)[NCOL]) {
-  if constexpr (l < CNT) {
-    if constexpr (l < 16) {
-      fmac_rowbcast<l, l == 0>(a2[l & 3], v0, R2[l]);
-      fmac_rowbcast<l, false>(a1[l & 3], v0, R1[l]);
-    } else {
-      fmac_rowbcast<l - 16, l == 16>(a2[l & 3], v1, R2[l]);
-      fmac_rowbcast<l - 16, false>(a1[l & 3], v1, R1[l]);
-    }
-    rowdot2<CNT, NCOL, l + 1>(a2, a1, v0, v1, R2, R1);
-  }
-}
-template <int CNT, int NCOL, int l = 0>
-__device__ __forceinline__ void rowdot1(double (&ac)[4], double v0, double v1, const double (&R)[NCOL]) {
-  if constexpr (l < CNT) {
-    if constexpr (l < 16) fmac_rowbcast<l, l == 0>(ac[l & 3], v0, R[l]);
-    else fmac_rowbcast<l - 16, l == 16>(ac[l & 3], v1, R[l]);
-    rowdot1<CNT, NCOL, l + 1>(ac, v0, v1, R);
-  }
-}
-// ac += R[l] * vec[l], l < CNT: ONE chain of multiply-adds (its latency is covered by the other waves of the SIMD; four partial sums
-// cost four register clears and three adds per product)
-template <int CNT, int NCOL, int l = 0>
+// ac += R[l] * vec[l], l < CNT; vec[l] = lane l of v0 (l < 16) or lane l - 16 of v1 of the reader's 16-lane row.  ONE chain of
+// multiply-adds (its latency is covered by the other waves of the SIMD; four partial sums cost four register clears and three adds
+// per product), emitted as one asm statement (step_body.h row_dot: no wait state between the links of the chain)
+template <int CNT, int NCOL, bool BLK = true>
 __device__ __forceinline__ void rowdot_one(double& ac, double v0, double v1, const double (&R)[NCOL]) {
-  if constexpr (l < CNT) {
-    if constexpr (l < 16) fmac_rowbcast<l, l == 0>(ac, v0, R[l]);
-    else fmac_rowbcast<l - 16, l == 16>(ac, v1, R[l]);
-    rowdot_one<CNT, NCOL, l + 1>(ac, v0, v1, R);
-  }
+  row_dot<CNT, BLK>(ac, v0, v1, R);
 }
 // R[l] += vec[l] * coef for l < CNT (coef is the lane's own); column LOWCOL only in lanes 0-31 (-1: none)
-template <int CNT, int NCOL, int LOWCOL, int l = 0>
+template <int CNT, int NCOL, int LOWCOL>
 __device__ __forceinline__ void rowupd(double (&R)[NCOL], double v0, double v1, double coef) {
-  if constexpr (l < CNT) {
-    if constexpr (l < 16) fmac_rowbcast_m<l, l == 0, l == LOWCOL>(R[l], v0, coef);
-    else fmac_rowbcast_m<l - 16, l == 16, l == LOWCOL>(R[l], v1, coef);
-    rowupd<CNT, NCOL, LOWCOL, l + 1>(R, v0, v1, coef);
-  }
+  row_upd<CNT, LOWCOL>(R, v0, v1, coef);
 }
 // compile-time loop: f(std::integral_constant<int, I>) for I = B .. E-1
 template <int B, int E, typename F> __device__ __forceinline__ void static_for(F&& f) {
