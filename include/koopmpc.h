@@ -341,6 +341,10 @@ int kmpc_profile_enable(kmpc_handle* h, int on);
 int kmpc_profile_read(kmpc_handle* h, double* ms2, int64_t* count, int reset);
 /* 1 if kmpc_rollout runs as one fused kernel for this handle's configuration, else 0         */
 int kmpc_rollout_is_fused(const kmpc_handle* h);
+/* the route the last kmpc_rollout (steps > 0) of this handle took: 0 per-step launches (or no roll-out yet), 1 the fused
+ * generic kernel, 2 the fused default-option kernel -- the instantiation for handles created with the default options and
+ * rolled out without a log; same results either way                                              */
+int kmpc_rollout_variant(const kmpc_handle* h);
 /* Where that kernel comes from.  The reference's dimensions are constants edited in its scripts (duffing.py:66 Nlift, :632-633
  * MPCHorizon; Koopman_update.m:67, 70, 113: L = 10, N = 10), so the fused roll-out is not tied to a list: libkoopmpc.so holds the
  * instantiations of the BASELINE / reference dimension sets, and kmpc_create makes the kernel of any other set as a PLUG-IN --

@@ -18,6 +18,7 @@ namespace kmpc {
 //   KMPC_QP_NO_HGLOBAL        shared-model solve stages H into LDS        KMPC_SHARED_TWO_KERNELS  round-1 shared_solve + shared_condense
 //   KMPC_SHARED_MODEL_R3      round-3 model kernel (eight waves)          KMPC_SHARED_LIFT_GRAM_2  lift and Gram sums as two launches
 //   KMPC_SHARED_NO_FAST       every trajectory through the QP kernel      KMPC_SHARED_NO_LIST      solve-only kernel: one workgroup per trajectory
+//   KMPC_ROLLOUT_GENERIC      the fused roll-out never takes its default-option kernel (rollout_kernel.hip; read once per process)
 const char* dbg_env(const char* name);
 
 
@@ -222,6 +223,9 @@ struct RolloutPlugin { RolloutPluginKey key{}; rollout_plugin_fn fn = nullptr; }
 // the fused roll-out; a dimension set without a built-in instantiation (and every TERM launch) runs on `plugin`, at the workgroup size
 // the plug-in was made for -- a launch never looks up or compiles one
 template <typename T> hipError_t launch_rollout_fused(const RolloutArgs<T>& a, hipStream_t s, const RolloutPlugin* plugin);
+// which kernel the last launch_rollout_fused of the calling thread ran: 1 the generic one (built-in or plug-in), 2 the default-option
+// instantiation (step_body.h RoOpt: every option of the launch had the value that kernel fixes)
+int rollout_last_variant();
 bool rollout_builtin(int L, int N, int q, bool io32);  // libkoopmpc.so itself holds the instantiations of this set
 // the plug-in a launch of this configuration needs; false: none (built-in set, or the set does not fit the fused kernel at all)
 // (term: the variant with the per-step terminal refresh -- always a plug-in, also for the built-in sets; diag: the variant with the

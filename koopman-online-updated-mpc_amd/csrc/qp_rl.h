@@ -159,26 +159,28 @@ struct QpCarry {  // what a solve leaves for the next one (registers of the step
 // (An active-set continuation in registers for crawling solves was built and measured in round 5 -- 14 more spilled vector registers and
 //  3.3 % of the settled cfg2 window for solves that are 1 in 10 000 there, profiles/r5_cfg2_active_set_ab.txt -- and is not in this header:
 //  tools/experiments/qp_rl_active_set_variant.h.txt.  Crawling solves are finished by the active-set loop of qp_lds, step_v2.h.)
-template <int N_, typename IOT = double>
+// OPT: the compile-time option set (step_body.h RoOpt)
+template <int N_, typename IOT = double, int OPT = RO_OPT_GENERIC>
 __device__ __forceinline__ bool qp_rl(double* const sR, const double* sf, const StepArgs<double>& a, const StepVar<double>& sv, const int b,
                                       double* qx_out, double* u_slot, double (&M)[N_], double& rs, double& rsi, QpCarry& cs, double up, double xw_pre) {
   typedef double d2_t __attribute__((ext_vector_type(2)));
+  typedef RoOpt<OPT> O;
   static_assert(N_ <= 32, "qp_rl: one variable per lane of a 32-lane half (ownmask, row_newbcast index, diagonal lane)");
   const int tid = local_tid<64>(), half = tid >> 5, t = tid & 31;
   const bool own = t < N_;
   const int B = a.B;
-  const double uprev = a.du_mode ? up : 0.0;
+  const double uprev = O::du_mode(a) ? up : 0.0;
   double lb = a.lb, ub = a.ub;
   const double tol = Tol<double>::kkt();
   const double eact = Tol<double>::act() * (ub - lb);
   const double xmaxb = tabs(lb) > tabs(ub) ? tabs(lb) : tabs(ub);
-  if (a.du_mode && t == 0) {  // first increment: absolute input range folded in (Tank_System.m:182-188)
+  if (O::du_mode(a) && t == 0) {  // first increment: absolute input range folded in (Tank_System.m:182-188)
     lb = (a.umin - uprev) > lb ? (a.umin - uprev) : lb;
     ub = (a.umax - uprev) < ub ? (a.umax - uprev) : ub;
   }
   const double c0 = tclip(0.0, lb, ub);
-  const bool warm = a.x_warm != nullptr, predict_on = (a.qp_predict & 1) != 0;  // (read once: inside the loops every use was a scalar load)
-  const int max_iter = a.max_iter;
+  const bool warm = O::warm(a), predict_on = O::predict(a);  // (read once: inside the loops every use was a scalar load)
+  const int max_iter = O::max_iter(a, N_);
   constexpr unsigned ownmask = N_ >= 32 ? 0xffffffffu : ((1u << N_) - 1u);
   const int rowi = own ? t : N_ - 1;
   constexpr int NS = rl_stride(N_);
@@ -446,15 +448,15 @@ __device__ __forceinline__ bool qp_rl(double* const sR, const double* sf, const 
     return true;
   }
   if (own && !half) {
-    if (a.Useq) io_st<IOT>(a.Useq, (size_t)t * B + b, x);
-    if (a.x_warm) a.x_warm[(size_t)t * B + b] = x;
+    if (O::has_useq(a)) io_st<IOT>(a.Useq, (size_t)t * B + b, x);
+    if (O::warm(a)) a.x_warm[(size_t)t * B + b] = x;
   }
   if (tid == 0) {
-    const double uout = a.du_mode ? uprev + x : x;  // U0 = U0 + dU*(1)   (Tank_System.m:192)
+    const double uout = O::du_mode(a) ? uprev + x : x;  // U0 = U0 + dU*(1)   (Tank_System.m:192)
     *u_slot = x;  // (the first move, for a covariance update done ahead: step_v2.h)
-    if (sv.U0) io_st<IOT>(sv.U0, b, uout);
-    if (a.u_store) a.u_store[b] = uout;
-    if (a.plant >= 0) {  // x_loc = f_update(0, x_loc, u_loc)   (duffing.py:871)
+    if (O::has_u0(sv)) io_st<IOT>(sv.U0, b, uout);
+    if (O::has_u_store(a)) a.u_store[b] = uout;
+    if (O::has_plant(a)) {  // x_loc = f_update(0, x_loc, u_loc)   (duffing.py:871)
       double x1, x2;  // (x_next, when given, is the roll-out's LDS slot -- step_body.h lds_ld: as a select of two addresses these were
       // flat loads, which wait for both counters: behind the step's write-back a drain of every outstanding store, K = 20 - 4 %)
       if (sv.x_next) { x1 = lds_ld(sv.x_next); x2 = lds_ld(sv.x_next + 1); }

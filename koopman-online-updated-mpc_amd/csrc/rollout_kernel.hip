@@ -230,8 +230,15 @@ __device__ __attribute__((noinline)) void ro_encoder_tiles(const int wv_, const 
 // DIAG: with the diagnostics logs (RolloutArgs::diag, Psi_log, dA_log, dB_log, dC_log: the reference's logXLOClift and A_error, B_error,
 // C_error, duffing.py:850, 985-990): the lift's result also goes to Psi_log, the RLS phase of the register-state step stores the norms of
 // the change it makes (step_v2's DIAG).  Float64 register-state sets; always plug-ins too (kmpc_set_rollout_diagnostics loads them).
-template <int L_, int N_, int Q_, int NW, int KS_, typename IOT = double, bool TERM = false, bool DIAG = false>
+// OPT: the option set fixed at compile time (step_body.h RoOpt).  RO_OPT_DEFAULT -- the handle a controller created with its defaults
+// launches without a log, DESIGN.md 4.1 -- is the generic kernel without the branches of the other option values; it carries u_{k-1} from
+// step to step in scalar registers.  (Holding further step arguments in scalar registers across the loop was measured group by group and
+// raised the spill count every time: profiles/default_option_kernel.txt, tools/experiments/rollout_held_arguments.h.txt.)
+template <int L_, int N_, int Q_, int NW, int KS_, typename IOT = double, bool TERM = false, bool DIAG = false, int OPT = RO_OPT_GENERIC>
 __global__ __launch_bounds__((ro_max_threads<L_, N_, Q_, NW, KS_>())) void rollout_kernel(const RolloutArgs<double> ra) {
+  typedef RoOpt<OPT> O;
+#define RO_NO_UPDATE (O::D ? 0 : R.no_update)  /* (the default-option kernel always updates) */
+  static_assert(!O::D || (ro_v2<L_, N_, Q_>() && sizeof(IOT) == 8 && !TERM && !DIAG && (KS_ < 0 || NW == 16)), "default-option roll-out: float64 register-state sets");
   static_assert(sizeof(IOT) == 8 || ro_v2<L_, N_, Q_>(), "float32 I/O: register-state dimension sets only");
   static_assert(!DIAG || (sizeof(IOT) == 8 && ro_v2<L_, N_, Q_>()), "diagnostics: float64 register-state dimension sets only");
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
@@ -287,12 +294,21 @@ __global__ __launch_bounds__((ro_max_threads<L_, N_, Q_, NW, KS_>())) void rollo
   double psi_prev_reg = 0.0;
   if (live && ra.have_prev && (int)(tid0 & PSI_MASK) < L) psi_prev_reg = ra.psi[ra.cur ^ 1][(size_t)b * L + (tid0 & PSI_MASK)];
   typedef const RolloutArgs<double> __attribute__((address_space(4))) * kernarg_ptr_t;
+  // default-option kernel: the LDS offsets of the per-wave regions stay in scalar registers across the step loop
+  int h_wbase = ra.wbase, h_wstride = ra.wstride;
+  double u_carry = 0.0;  // u_{k-1} (default-option kernel, k > 0): what this wave's solve of the step before left
+  (void)u_carry; (void)h_wbase; (void)h_wstride;
   for (int k = 0; k < ra.steps; ++k) {
     // The step arguments stay in the kernel-argument segment and are re-read where they are used: hoisted out
     // of this loop they would pin ~150 scalar registers for the whole kernel (the asm hides the loop invariance).
     kernarg_ptr_t kp = (kernarg_ptr_t)__builtin_amdgcn_kernarg_segment_ptr();
     asm volatile("" : "+s"(kp));
     const RolloutArgs<double> __attribute__((address_space(4)))& R = *kp;
+    if constexpr (O::D) {
+      // (opaque once per step: the addresses derived from them are recomputed per step as in the generic kernel, not hoisted out of
+      //  the loop into registers of their own)
+      asm volatile("" : "+s"(h_wbase), "+s"(h_wstride));
+    }
     const StepArgs<double>& a = *(const StepArgs<double>*)(&kp->s);  // psi strides (1, L), accumulate = 1: host
     // (as local_tid: lane- and wave-derived addresses and the lift's tiling constants are recomputed in every
     //  iteration instead of being carried across the step in registers)
@@ -433,14 +449,16 @@ __global__ __launch_bounds__((ro_max_threads<L_, N_, Q_, NW, KS_>())) void rollo
         // the end of the previous step: they are the oldest of their SIMDs and finish the step body first.)
         __syncthreads();
         if constexpr (V2) {
-          if (live && k > 0 && !R.no_update) {
-            int woff0 = R.wbase + wv * R.wstride, bk0 = b;
+          if (live && k > 0 && !RO_NO_UPDATE) {
+            int woff0 = (O::D ? h_wbase : R.wbase) + wv * (O::D ? h_wstride : R.wstride), bk0 = b;
             asm volatile("" : "+s"(woff0), "+s"(bk0));
             double* const wsm0 = smem + woff0;
-            const double uk = a.u_prev[bk0];  // u_{k-1}: the previous step stored it (u_store) when its solve ended
+            double uk;  // u_{k-1}: the previous step stored it (u_store) when its solve ended
+            if constexpr (O::D) uk = u_carry;
+            else uk = a.u_prev[bk0];
             const int t0 = lane & 31;
             const double z0 = t0 < L_ ? psi_prev_reg : (t0 == L_ ? uk : 0.0);
-            const double gains0 = v2_rls_cov<L_, true>(R.img + (size_t)bk0 * R.img_stride, z0, a.lam);
+            const double gains0 = v2_rls_cov<L_, true>(R.img + (size_t)bk0 * R.img_stride, z0, O::lam(a));
             if (lane < 32 || t0 < L_) v2_cov_slot<N_>(wsm0)[v2_cov_index<L_>(lane)] = gains0;
           } else {
             __syncthreads();
@@ -542,7 +560,7 @@ __global__ __launch_bounds__((ro_max_threads<L_, N_, Q_, NW, KS_>())) void rollo
     }
 #endif
     if (live) {
-      int woff = R.wbase + wv * R.wstride, bk = b;
+      int woff = (O::D ? h_wbase : R.wbase) + wv * (O::D ? h_wstride : R.wstride), bk = b;
       asm volatile("" : "+s"(woff), "+s"(bk));  // (as local_tid: keeps the step's address arithmetic inside the loop)
       double* const wsm = smem + woff;
       double* const psi_now = R.psi[cur];
@@ -561,15 +579,17 @@ __global__ __launch_bounds__((ro_max_threads<L_, N_, Q_, NW, KS_>())) void rollo
       sv.psi_in_regs = 1;
       sv.psi_now_v = psi_i;
       sv.psi_prev_v = psi_prev_reg;
-      sv.phases = PH_CONDENSE | PH_QP | ((have_prev && !R.no_update) ? PH_RLS : 0);
+      sv.phases = PH_CONDENSE | PH_QP | ((have_prev && !RO_NO_UPDATE) ? PH_RLS : 0);
       sv.first_update = fresh ? 1 : 0;
       sv.plant_switched = (R.switch_step >= 0 && R.step0 + k >= R.switch_step) ? 1 : 0;
-      sv.U0 = R.U_log ? io_at<IOT>(R.U_log, (size_t)k * B) : a.U0;
+      if constexpr (O::D) sv.U0 = a.U0;
+      else sv.U0 = R.U_log ? io_at<IOT>(R.U_log, (size_t)k * B) : a.U0;
+      if constexpr (O::D) { sv.u_prev_in_regs = k > 0 ? 1 : 0; sv.u_prev_v = u_carry; }
       sv.x_next = RBF ? nullptr : sXn + wv * 4;
-      sv.cov_done = (k > 0 && !R.no_update) ? 1 : 0;
+      sv.cov_done = (k > 0 && !RO_NO_UPDATE) ? 1 : 0;
       // (waves without an encoder tile do the next step's covariance half inside the next lift instead: see above)
       const bool tile_wave = RBF || NW == 4 || wv < ((KS_ > 0 ? (KS_ <= 28 ? 112 : 128) : R.Hp) >> 4) || wv < (R.Lp >> 4);
-      sv.cov_ahead = (k + 1 < R.steps && !R.no_update && tile_wave) ? 1 : 0;
+      sv.cov_ahead = (k + 1 < R.steps && !RO_NO_UPDATE && tile_wave) ? 1 : 0;
       if constexpr (DIAG) {
         if (!(sv.phases & PH_RLS) && lane == 0) {  // (no update in this step: the model did not move)
           if (dgo.dA) io_st<IOT>(dgo.dA, 0, 0.0);
@@ -620,11 +640,13 @@ __global__ __launch_bounds__((ro_max_threads<L_, N_, Q_, NW, KS_>())) void rollo
         else step_body<double, 64, L_, N_, Q_, LOWREG, !LOWREG || Q_ == L_, ro_one_region<L_, N_, Q_, KS_>()>(a, sv2, bk, wsm);
       } else if constexpr (V2) {
         double* imgb = R.img + (size_t)bk * R.img_stride;
-        step_v2<L_, N_, Q_, LOWREG, !LOWREG, IOT, 0, DIAG>(a, sv, bk, wsm, imgb, &dgo);
+        step_v2<L_, N_, Q_, LOWREG, !LOWREG, IOT, 0, DIAG, OPT>(a, sv, bk, wsm, imgb, &dgo);
+        // (the first move of the solve, where it left it for the covariance update done ahead; no delta-u form in this kernel: it IS u_k)
+        if constexpr (O::D) u_carry = uniform_value(lds_ld(v2_u_slot<L_, N_>(wsm)));
       } else {
         step_body<double, 64, L_, N_, Q_, LOWREG, !LOWREG || Q_ == L_, ro_one_region<L_, N_, Q_, KS_>()>(a, sv, bk, wsm);
       }
-      if (R.X_log) {
+      if (!O::D && R.X_log) {
         __threadfence_block();
         if (lane < n) io_st<IOT>(R.X_log, ((size_t)k * n + lane) * B + b, io_ld<IOT>(a.X_rw, (size_t)lane * B + b));
       }
@@ -658,6 +680,7 @@ __global__ __launch_bounds__((ro_max_threads<L_, N_, Q_, NW, KS_>())) void rollo
 }
 
 
+#undef RO_NO_UPDATE
 // waves (= trajectories) per workgroup of the fused roll-out.  MLP lift: 16 (one workgroup per CU) or 8 (two per
 // CU); the RBF lift needs no cooperation, so the workgroup is as large as the per-trajectory LDS regions allow.
 // 0: does not fit.
@@ -727,22 +750,45 @@ static int rollout_waves(int n, int L, int q, int N, bool rbf, int Lp, int B = 1
     if (rollout_lds_elems(n, L, q, N, true, w, Lp, nullptr) <= cap) return w;
   return 0;
 }
-template <int L_, int N_, int Q_, int NW, int KS_, typename IOT = double, bool TERM = false, bool DIAG = false>
+template <int L_, int N_, int Q_, int NW, int KS_, typename IOT = double, bool TERM = false, bool DIAG = false, int OPT = RO_OPT_GENERIC>
 static hipError_t launch_rollout_nw(const RolloutArgs<double>& k, int waves, size_t lds, hipStream_t s) {
   static size_t configured_dev[16] = {};  // (function attributes are per device)
   size_t& configured = configured_dev[device_slot()];
   if (lds > 64 * 1024 && lds > configured) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&rollout_kernel<L_, N_, Q_, NW, KS_, IOT, TERM, DIAG>),
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&rollout_kernel<L_, N_, Q_, NW, KS_, IOT, TERM, DIAG, OPT>),
                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;
     configured = lds;
   }
   const int grid = (k.s.B + waves - 1) / waves;
-  hipLaunchKernelGGL((rollout_kernel<L_, N_, Q_, NW, KS_, IOT, TERM, DIAG>), dim3(grid), dim3(64 * waves), lds, s, k);
+  hipLaunchKernelGGL((rollout_kernel<L_, N_, Q_, NW, KS_, IOT, TERM, DIAG, OPT>), dim3(grid), dim3(64 * waves), lds, s, k);
   return hipGetLastError();
 }
 
+// The default-option kernel (RO_OPT_DEFAULT) serves a launch only if EVERY option it fixes has its fixed value in this launch -- the list
+// of DESIGN.md 4.1, one test per line of it; everything else, and every launch under KMPC_ROLLOUT_GENERIC (measurement / test aid: the A
+// side of the A/B), runs the generic kernel.
+static bool rollout_default_options(const RolloutArgs<double>& a) {
+  const StepArgs<double>& s = a.s;
+  return s.lam == 1.0 && s.du_mode == 0 && s.cy0 == 0 && s.c_skip_first == 0 && s.ref_per_traj == 0 && s.Wterm == nullptr && s.wterm_per_traj == 0 &&
+         s.x_warm != nullptr && (s.qp_predict & 1) == 1 && s.max_iter == 8 * s.N + 40 && s.Useq == nullptr && s.U0 != nullptr && s.u_store != nullptr &&
+         s.u_prev == s.u_store && s.plant >= 0 && s.n == 2 && a.no_update == 0 && a.U_log == nullptr && a.X_log == nullptr && a.io_f32 == 0 &&
+         a.term_every == 0 && a.diag == 0;
+}
+// 1: the last launch of this thread ran the generic kernel (built-in or plug-in), 2: the default-option kernel
+static thread_local int g_rollout_last_variant = 0;
+#if !defined(KMPC_ROLLOUT_JIT_TU) && !defined(KMPC_ROLLOUT_IO32_TU)
+int rollout_last_variant() { return g_rollout_last_variant; }
+#endif
 // waves_in > 0: the workgroup size is the caller's decision (plug-ins: the library made it with rollout_waves)
+// the dimension sets with a default-option instantiation: (20, 20, 2) -- BASELINE cfg2, MLP lift -- and (8, 30, 2) -- cfg3, RBF lift
+template <int L_, int N_, int Q_> constexpr bool ro_default_built() {
+#ifdef KMPC_ROLLOUT_JIT_TU
+  return false;
+#else
+  return Q_ == 2 && ((L_ == 20 && N_ == 20) || (L_ == 8 && N_ == 30));
+#endif
+}
 template <int L_, int N_, int Q_, typename IOT = double> static hipError_t launch_rollout_impl(const RolloutArgs<double>& a, hipStream_t s, int waves_in = 0) {
   RolloutArgs<double> k = a;
   const bool rbf = a.lift_rbf != 0;
@@ -782,6 +828,16 @@ template <int L_, int N_, int Q_, typename IOT = double> static hipError_t launc
   return launch_rollout_nw<L_, N_, Q_, JNW, JKS, IOT, KMPC_JIT_TERM != 0, KMPC_JIT_DIAG != 0>(k, waves, lds, s);
 #else
   if (rbf && a.rbf_matlab > 1) return hipErrorInvalidValue;  // (rbf.m's other kinds are always plug-ins: launch_rollout_fused)
+  g_rollout_last_variant = 1;
+  if constexpr (sizeof(IOT) == 8 && ro_default_built<L_, N_, Q_>()) {
+    static const bool generic = dbg_env("KMPC_ROLLOUT_GENERIC") != nullptr;  // measurement / test aid: the generic kernel for every launch
+    // ((20, 20, 2): the MLP lift, sixteen waves, the reference's encoder width; (8, 30, 2): the RBF lift)
+    if (!generic && rollout_default_options(a) && (L_ == 20 ? (!rbf && waves == 16 && ks25) : rbf)) {
+      g_rollout_last_variant = 2;
+      if constexpr (L_ == 20) return launch_rollout_nw<L_, N_, Q_, 16, 25, IOT, false, false, RO_OPT_DEFAULT>(k, waves, lds, s);
+      else return launch_rollout_nw<L_, N_, Q_, 16, -1, IOT, false, false, RO_OPT_DEFAULT>(k, waves, lds, s);
+    }
+  }
   if (rbf) return launch_rollout_nw<L_, N_, Q_, 16, -1, IOT>(k, waves, lds, s);
   if constexpr (sizeof(IOT) == 4) {  // (float32 I/O: workgroups of sixteen and eight trajectories -- what rollout_waves picks for these sets)
     if (waves == 16) return ks25 ? launch_rollout_nw<L_, N_, Q_, 16, 25, IOT>(k, waves, lds, s) : launch_rollout_nw<L_, N_, Q_, 16, 0, IOT>(k, waves, lds, s);
@@ -879,6 +935,7 @@ bool rollout_plugin_key(int n, int L, int N, int q, bool rbf, int Lp, int KS, in
 }
 static hipError_t launch_rollout_plugin(const RolloutArgs<double>& a, const RolloutPlugin* p, hipStream_t s) {
   if (!p || !p->fn) return hipErrorInvalidValue;
+  g_rollout_last_variant = 1;  // (a plug-in is always the generic kernel)
   // (the RBF object serves every workgroup size: rollout_waves picks it as for a built-in set)
   const int waves = p->key.ks < 0 ? rollout_waves(a.s.n, a.s.L, a.s.q, a.s.N, true, a.Lp, a.s.B) : p->key.nw;
   return p->fn(&a, waves, s);
@@ -890,7 +947,7 @@ template <> hipError_t launch_rollout_fused<double>(const RolloutArgs<double>& a
   if (!a.lift_rbf && (a.Hp > 128 || (a.Hp & 15) || a.Lp > 64 || a.KS > 32 || a.nhh < 0 || a.nhh > 2 || a.s.n > 4))
     return hipErrorInvalidValue;
   if (a.term_every > 0 || a.diag || (a.lift_rbf && a.rbf_matlab > 1) || !rollout_builtin(a.s.L, a.s.N, a.s.q, a.io_f32 != 0)) return launch_rollout_plugin(a, plugin, s);
-  if (a.io_f32) return launch_rollout_io32(a, s);
+  if (a.io_f32) { g_rollout_last_variant = 1; return launch_rollout_io32(a, s); }
   using IOT = double;
   KMPC_ROLLOUT_SETS_F64(KMPC_SET_LAUNCH)
   return hipErrorInvalidValue;

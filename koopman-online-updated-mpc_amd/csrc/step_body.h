@@ -105,6 +105,34 @@ template <typename T> struct StepVar {
   // register-state step (step_v2.h): the covariance half of this step's RLS update was done at the end of the previous step /
   // is to be done for the next one at the end of this step
   int cov_done = 0, cov_ahead = 0;
+  // default-option roll-out (RoOpt below): u_{k-1} comes from the step before in scalar registers instead of StepArgs::u_prev[b]
+  int u_prev_in_regs = 0;
+  T u_prev_v = T(0);
+};
+
+// Option set of the fused roll-out that is fixed at compile time (template parameter OPT of rollout_kernel, step_v2 and qp_rl).
+//   RO_OPT_GENERIC  every option is a launch argument, tested where it is used
+//   RO_OPT_DEFAULT  the options of the handle KoopmanMPC(n=2, L, N, batch, weights=...) creates with its defaults, launched by
+//                   rollout(plant, X, r, steps) without a log -- the list is DESIGN.md 4.1; launch_rollout_impl checks every one of them
+//                   before it picks this kernel.  The accessors return the fixed values as constants: the branches of the other values
+//                   and the argument reads behind them are not in that kernel.  The arithmetic of a trajectory is the generic kernel's.
+enum { RO_OPT_GENERIC = 0, RO_OPT_DEFAULT = 1 };
+template <int OPT> struct RoOpt {
+  static constexpr bool D = OPT == RO_OPT_DEFAULT;
+  typedef StepArgs<double> A;
+  static __device__ __forceinline__ double lam(const A& a) { if constexpr (D) return 1.0; else return a.lam; }
+  static __device__ __forceinline__ int du_mode(const A& a) { if constexpr (D) return 0; else return a.du_mode; }
+  static __device__ __forceinline__ int cy0(const A& a) { if constexpr (D) return 0; else return a.cy0; }
+  static __device__ __forceinline__ int c_skip_first(const A& a) { if constexpr (D) return 0; else return a.c_skip_first; }
+  static __device__ __forceinline__ int ref_per_traj(const A& a) { if constexpr (D) return 0; else return a.ref_per_traj; }
+  static __device__ __forceinline__ bool has_wterm(const A& a) { if constexpr (D) return false; else return a.Wterm != nullptr; }
+  static __device__ __forceinline__ bool warm(const A& a) { if constexpr (D) return true; else return a.x_warm != nullptr; }
+  static __device__ __forceinline__ bool predict(const A& a) { if constexpr (D) return true; else return (a.qp_predict & 1) != 0; }
+  static __device__ __forceinline__ int max_iter(const A& a, int N) { if constexpr (D) return 8 * N + 40; else return a.max_iter; }
+  static __device__ __forceinline__ bool has_useq(const A& a) { if constexpr (D) return false; else return a.Useq != nullptr; }
+  static __device__ __forceinline__ bool has_u_store(const A& a) { if constexpr (D) return true; else return a.u_store != nullptr; }
+  static __device__ __forceinline__ bool has_plant(const A& a) { if constexpr (D) return true; else return a.plant >= 0; }
+  template <typename SV> static __device__ __forceinline__ bool has_u0(const SV& sv) { if constexpr (D) return true; else return sv.U0 != nullptr; }
 };
 
 // e = tid, tid + TPB, ... < count.  With a compile-time COUNT the loop is fully unrolled, so that the loads of all

@@ -162,6 +162,8 @@ __device__ __forceinline__ double v2_rls_cov(double* const img, const double z, 
 // first move of the last solve
 template <int N_> __device__ __forceinline__ double* v2_cov_slot(double* sm) { return sm + v2_region1(N_) + 66; }
 // (its element of lane `lane`: lanes 0-31 as they are, lanes 32 .. 32+L-1 behind them; the other lanes of the upper half share the last slot)
+// (the first move of the last solve: qp_rl's u_slot, red[15] of step_v2's map)
+template <int L_, int N_> __device__ __forceinline__ double* v2_u_slot(double* sm) { return sm + v2_region1(N_) + v2_carry_elems(L_) + 15; }
 template <int L_> __device__ __forceinline__ int v2_cov_index(int lane) { return lane < 32 ? lane : (lane - 32 < L_ ? lane : 32 + L_ - 1 + (L_ & 1)); }
 
 // sv.psi_now_v / psi_prev_v: lane with (lane & 31) = i < L carries psi_i (BOTH halves).  img: this trajectory's wave image.
@@ -172,10 +174,12 @@ template <int L_> __device__ __forceinline__ int v2_cov_index(int lane) { return
 //   A, B and C -- rank one with lam = 1: |e| |g[0:L]|, |e| |g[L]|, |e_c| |h| -- and lane 0 stores them at dg (null pointers are skipped);
 //   a first update (K_A = 0, bar_X = 0: full rank against the model in use) stores quiet NaNs.  Without it the code is what it was.
 struct V2DiagOut { double* dA; double* dB; double* dC; };
-template <int L_, int N_, int Q_, bool LOWREG, bool ASREG, typename IOT = double, int PART = 0, bool DIAG = false>
+// OPT: the compile-time option set (step_body.h RoOpt); the default-option roll-out also hands u_{k-1} over in registers (sv.u_prev_in_regs)
+template <int L_, int N_, int Q_, bool LOWREG, bool ASREG, typename IOT = double, int PART = 0, bool DIAG = false, int OPT = RO_OPT_GENERIC>
 __device__ __forceinline__ void step_v2(const StepArgs<double>& a, const StepVar<double>& sv, const int b, double* const sm, double* const img,
                                         const V2DiagOut* const dg = nullptr) {
   typedef double d2_t __attribute__((ext_vector_type(2)));
+  typedef RoOpt<OPT> O;
   constexpr int P_ = L_ + 1, CP = (L_ + 2) / 2, NC = 2 * CP, NX = 2, S2 = 2 * L_ + 1, S1 = L_ + NX;
   constexpr int N = N_, q = Q_;
   static_assert(step_v2_dims(L_, N_, Q_), "step_v2: dimension set");
@@ -199,12 +203,14 @@ __device__ __forceinline__ void step_v2(const StepArgs<double>& a, const StepVar
   double* const qg = qxa + N;
 
   KTRACE(0);
-  const double up = uniform_value(a.u_prev[b]);  // (one trajectory per wave: scalar registers; K = 200 - 2 %)
+  double up;  // (one trajectory per wave: scalar registers; K = 200 - 2 %)
+  if (O::D && sv.u_prev_in_regs) up = sv.u_prev_v;
+  else up = uniform_value(a.u_prev[b]);
   double xw_pre = 0.0;
   constexpr int REFN = (Q_ * N_ + 63) / 64;
   double refp[REFN];
   if (sv.phases & PH_CONDENSE) {
-    const double* refg = io_at<IOT>(a.ref, a.ref_per_traj ? (size_t)b * q * N : 0);
+    const double* refg = io_at<IOT>(a.ref, O::ref_per_traj(a) ? (size_t)b * q * N : 0);
 #pragma unroll
     for (int i = 0; i < REFN; ++i) {
       const int e = tid + i * 64, ec = e < q * N ? e : 0, k = ec / q, r = ec - k * q;
@@ -243,7 +249,7 @@ __device__ __forceinline__ void step_v2(const StepArgs<double>& a, const StepVar
     // z = [psi(x_{k-1}); u_{k-1}] in the lanes of both halves
     const double z = t < L_ ? sv.psi_prev_v : (t == L_ ? up : 0.0);
     KTRACE(1);
-    const double u2 = sv.cov_done ? sCov[v2_cov_index<L_>(tid)] : v2_rls_cov<L_, false>(img, z, a.lam);
+    const double u2 = sv.cov_done ? sCov[v2_cov_index<L_>(tid)] : v2_rls_cov<L_, false>(img, z, O::lam(a));
     KTRACE(2);
     double zv0, zv1;
     gather_rows<(S1 > P_ ? S1 : P_)>(z, zv0, zv1);
@@ -260,15 +266,15 @@ __device__ __forceinline__ void step_v2(const StepArgs<double>& a, const StepVar
       gather_rows<(S1 > P_ ? S1 : P_)>(hall, h0, h1);
       const bool isK = t < L_, isC = t >= L_ && t < S1;
       double eK = psin - acc1;
-      if (a.lam != 1.0) {
-        const double linv = 1.0 / a.lam;
+      if (O::lam(a) != 1.0) {
+        const double linv = 1.0 / O::lam(a);
         eK = eK * linv + psin * (1.0 - linv);
         const double sc = isK ? linv : 1.0;
 #pragma unroll
         for (int c = 0; c < P_; ++c) R1[c] *= sc;
       }
       const double cK = isK ? eK : 0.0;
-      const double cC = (isC && !(a.c_skip_first && fu)) ? xn - acc1 : 0.0;
+      const double cC = (isC && !(O::c_skip_first(a) && fu)) ? xn - acc1 : 0.0;
       rowupd<P_, NC, -1>(R1, g0, g1, cK);
       rowupd<L_, NC, -1>(R1, h0, h1, cC);
       if constexpr (DIAG) {
@@ -319,9 +325,9 @@ __device__ __forceinline__ void step_v2(const StepArgs<double>& a, const StepVar
     double v0, v1;
     gather_rows<S1>(isA ? (half ? psin : R1[L_]) : 0.0, v0, v1);
     // delta-u form (Tank_System.m:110-113): x+ = A x + B s, s = 1 on the v chain and u_prev on the w chain
-    const double bs = (a.du_mode && isA) ? R1[L_] * (half ? up : 1.0) : 0.0;
+    const double bs = (O::du_mode(a) && isA) ? R1[L_] * (half ? up : 1.0) : 0.0;
     // the rows of C_o give g_j = C_o v_j and C_o w_j at step j (j = 0 .. N)
-    const int ro = t - L_ - a.cy0;
+    const int ro = t - L_ - O::cy0(a);
     const bool isO = ro >= 0 && ro < q;
     double* const optr = isO ? (half ? sEr - q + ro : sG + ro) : dump + tid;
     KTRACE(5);
@@ -344,7 +350,7 @@ __device__ __forceinline__ void step_v2(const StepArgs<double>& a, const StepVar
     block_sync<64>();
   }
   KTRACE(6);
-  if ((sv.phases & PH_QP) && a.x_warm) xw_pre = a.x_warm[(size_t)(t < N_ ? t : 0) * a.B + b];
+  if ((sv.phases & PH_QP) && O::warm(a)) xw_pre = a.x_warm[(size_t)(t < N_ ? t : 0) * a.B + b];
   // the tableau of the last solve leaves LDS before H takes its place
   double M[N_];
   double rs = 1.0, rsi = 1.0;
@@ -413,7 +419,7 @@ __device__ __forceinline__ void step_v2(const StepArgs<double>& a, const StepVar
     });
     if (hf && idx < N_) sf[idx] = 2.0 * Qw * acc;
   }
-  if (a.Wterm) {
+  if (O::has_wterm(a)) {
     // terminal block of Q_bar is PN instead of Qw I (Koopman_update.m:381); Wterm = PN - Qw I:
     //   H[a][b] += g_{N-1-a}' sym(W) g_{N-1-b},   f[a] += 2 g_{N-1-a}' W e_N
     block_sync<64>();
@@ -447,7 +453,7 @@ __device__ __forceinline__ void step_v2(const StepArgs<double>& a, const StepVar
   // phase 3: box QP (rows in lanes, carried tableau: qp_rl.h)
   // =====================================================================================
   if (sv.phases & PH_QP) {
-    if (qp_rl<N_, IOT>(sR, sf, a, sv, b, qxo, red + 15, M, rs, rsi, cs, up, xw_pre)) {
+    if (qp_rl<N_, IOT, OPT>(sR, sf, a, sv, b, qxo, red + 15, M, rs, rsi, cs, up, xw_pre)) {
       // crawling solve (rare): H moves to this trajectory's global scratch block, the active-set loop of qp_lds works with an
       // LDS tableau in its place
 #ifdef KMPC_TRACE
@@ -477,8 +483,8 @@ __device__ __forceinline__ void step_v2(const StepArgs<double>& a, const StepVar
     block_sync<64>();
     if (sv.cov_ahead) {
       // the covariance half of the NEXT step's update: its regressor [psi(x_k); u_k] is complete now
-      const double uk = (a.du_mode ? up : 0.0) + red[15];  // (the solve leaves its first move there)
-      const double gains = v2_rls_cov<L_, false>(img, t < L_ ? psin : (t == L_ ? uk : 0.0), a.lam);
+      const double uk = (O::du_mode(a) ? up : 0.0) + red[15];  // (the solve leaves its first move there)
+      const double gains = v2_rls_cov<L_, false>(img, t < L_ ? psin : (t == L_ ? uk : 0.0), O::lam(a));
       if (!half || t < L_) sCov[v2_cov_index<L_>(tid)] = gains;
     }
   }

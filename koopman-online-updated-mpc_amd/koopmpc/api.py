@@ -652,6 +652,11 @@ class KoopmanMPC:
         """True if rollout() runs as one fused kernel launch for this configuration."""
         return bool(self.lib.kmpc_rollout_is_fused(self.h))
 
+    def rollout_variant(self):
+        """The route the last rollout() with steps > 0 took: 0 per-step launches (or no roll-out yet), 1 the fused generic kernel,
+        2 the fused default-option kernel (a controller created with the default options, rolled out without a log)."""
+        return int(self.lib.kmpc_rollout_variant(self.h))
+
     def rollout_plugin_status(self):
         """(code, text): where the fused roll-out kernel of this controller comes from -- 0 the library's own instantiation, 1 a
         plug-in made for this dimension set when the controller was created (text: its file, found in the kernel cache or compiled
