@@ -277,7 +277,7 @@ int kmpc_plant_step(kmpc_handle* h, int plant, void* X_dev, const void* U_dev, d
  * switch_step = 102; pass a negative value for "never").  Optional outputs: U_log_dev (steps x B),
  * X_log_dev (steps x n x B, the state AFTER each plant step), status_dev[B] (worst QP status of
  * each trajectory over the call), iters_dev[B] (its total number of Newton solves).
- * For single-wave configurations (kmpc_rollout_is_fused: n = 2, y = C x with q <= 2 or y = psi, (L+1)^2 and N^2 <= 2048, as far as
+ * For single-wave configurations (kmpc_rollout_is_fused: n = 2, y = C x with q <= 2 < L or y = psi, (L+1)^2 <= 2048, N <= 40, as far as
  * the LDS holds a workgroup) the whole
  * call is ONE kernel launch: 16 trajectories per workgroup, the encoder evaluated inside on MFMA, no
  * synchronisation between workgroups from the first step to the last.  Same results as the per-step

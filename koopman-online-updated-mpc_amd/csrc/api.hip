@@ -152,6 +152,10 @@ static void* resolve_nccl_allreduce() {
   } while (0)
 
 static inline long even_up(long v) { return (v + 1) & ~1L; }
+// what kmpc_rollout_plugin_status says (code 2) of a handle that Impl::fused_kind_ok refuses.  (kmpc_rollout_plugin_prebuild has no
+// output kind: by its contract out_rows == L, or out_rows = 0 with n == L, asks for the y = psi object, which is what it makes.)
+static const char* const kFusedKindReason =
+    "no fused roll-out: y = C x with as many output rows as lifted states (q == L), which the fused kernels read as y = psi (per-step launches)";
 // KMPC_PLANT_* with the optional KMPC_PLANT_RK4_MATLAB bit (not for the tank map, which has no Runge-Kutta step)
 static inline bool plant_id_ok(int plant) {
   const int base = plant & ~KMPC_PLANT_RK4_MATLAB;
@@ -224,8 +228,13 @@ struct Impl : kmpc_handle {
   }
   // this handle's dimension set can run fused at all (single-wave trajectories, two states, an instantiation or a plug-in that was not refused)
   bool fused_dims_ok() const {
-    return threads == 64 && n == 2 && variant[0][0].state >= 0 && rollout_fused_available<double>(n, L, N, q, threads, cfg.lift_kind != KMPC_LIFT_MLP);
+    return threads == 64 && n == 2 && fused_kind_ok() && variant[0][0].state >= 0 &&
+           rollout_fused_available<double>(n, L, N, q, threads, cfg.lift_kind != KMPC_LIFT_MLP);
   }
+  // (the fused kernels are static instantiations, which take the output kind from q -- Q_ == L_ means y = psi, step_body.h --: a handle
+  //  with y = C x and as many output rows as lifted states (n = 2, L = 2, both rows of C) would track psi(x).  It keeps the per-step
+  //  launches, whose launcher hands such a handle to the generic kernel: step_kernel.hip launch_step)
+  bool fused_kind_ok() const { return (q == L) == (cfg.output_kind == KMPC_OUT_LIFT); }
   // four-wave solver (threads = 256, float64): every trajectory's last tableau and its variable set, kept from step to step
   // (StepArgs::qp_carry); any change of the model from outside forgets them (the next solve starts from 2H)
   T* dQpCarry = nullptr;
@@ -1183,7 +1192,12 @@ struct Impl : kmpc_handle {
       if (v->state > 0) { if (text) *text = rollout_plugin_describe(v->plugin.key); return 1; }
       if (v->state < 0) { if (text) *text = v->msg; return -1; }
     }
-    if (!fused_rollout_ok()) { if (text) *text = "no fused roll-out for this configuration (per-step launches)"; return 2; }
+    if (!fused_kind_ok()) { if (text) *text = kFusedKindReason; return 2; }
+    if (!fused_rollout_ok()) {
+      if (text) *text = "no fused roll-out for this configuration (per-step launches): the fused kernels serve float64, n = 2, (L + 1)^2 <= 2048, "
+                        "horizons N <= 40 and q = 1, 2 or L output rows";
+      return 2;
+    }
     if (text) *text = "built-in instantiation of libkoopmpc.so";
     return 0;
   }

@@ -293,11 +293,17 @@ bool make_plugin(const RolloutPluginKey& k, Loaded* out, std::string* err) {
 // Dimension sets a plug-in can be generated for: what rollout_kernel's two step bodies cover with one wave per trajectory --
 //   y = C x with q <= 2 output rows: the register-state step (step_v2.h) for L + 2 <= 32, N <= 32; the LDS step (step_body.h) beyond,
 //   y = psi (q = L): the 8 x 8-grid step of step_body.h,
-// as far as sixteen / eight / four trajectories fit into a CU's LDS (the caller checks rollout_waves) and n = 2 (the plants).
+// as far as sixteen / eight / four trajectories fit into a CU's LDS (the caller checks rollout_waves), n = 2 (the plants) and N <= 40.
+// (q == L is read as y = psi: whether the handle's output kind agrees is the caller's question -- api.hip fused_kind_ok.)
+static constexpr int kRolloutMaxHorizon = 40;
 bool rollout_plugin_dims(int n, int L, int N, int q) {
   if (n != 2 || L < 2 || L > 64 || N < 2 || N > 64 || q < 1) return false;
   if (q != L && q > 2) return false;
   if ((long)(L + 1) * (L + 1) > 2048 || (long)N * N > 2048) return false;  // (beyond: four waves per trajectory, the per-step kernels)
+  // The one-wave step solves horizons up to 40 in registers (step_body.h qp_regs).  Beyond, it runs the LDS solver, whose N x N tableau
+  // needs a region that the roll-out's LDS layouts do not have (one region: none at all; two regions: sized without it where
+  // tableau_saves_lds): at (44, 45, 2) the tableau ran over the next trajectory's region and the status words.  Per-step launches.
+  if (N > kRolloutMaxHorizon) return false;
   return true;
 }
 

@@ -2175,9 +2175,12 @@ __device__ __forceinline__ void step_body(const StepArgs<T>& a, const StepVar<T>
         cur ^= 1;
       }
       }
-    } else if constexpr (L_ > 0 && TPB == 64 && (L_ + Q_ <= 64) && ((L_ & 1) == 0)) {
+    } else if constexpr (L_ > 0 && TPB == 64 && (L_ + Q_ <= 64) && ((L_ & 1) == 0 || ONE_REGION)) {
       // Static path for 32 < L + q <= 64 (cfg4 sizes): lane t keeps row t of [A; Co] in registers and
       // advances BOTH recursions (v and w) each step.
+      // (One region -- the fused roll-out's ONE64 -- takes this path for odd L as well, with 8-byte reads of the vectors: C may sit
+      //  where g is written, so its rows must be in registers before the first step, which the generic path below does not do; and
+      //  the one-region path further down is the four-wave kernel's.)
       const int t = tid;
       const int nco = cx ? q : 0;
       const bool isA = t < L, isC = (t >= L) && (t < L + nco);
@@ -2193,13 +2196,23 @@ __device__ __forceinline__ void step_body(const StepArgs<T>& a, const StepVar<T>
         const T2* v2 = reinterpret_cast<const T2*>(__builtin_assume_aligned(sV + cur * L, 2 * sizeof(T)));
         const T2* w2 = reinterpret_cast<const T2*>(__builtin_assume_aligned(sW + cur * L, 2 * sizeof(T)));
         T av[2] = {T(0), T(0)}, aw[2] = {T(0), T(0)};
+        if constexpr ((L_ & 1) == 0) {
 #pragma unroll
-        for (int l = 0; l < L_ / 2; ++l) {
-          const T2 xv = v2[l], xw = w2[l];
-          av[0] += row[2 * l] * xv.x;
-          av[1] += row[2 * l + 1] * xv.y;
-          aw[0] += row[2 * l] * xw.x;
-          aw[1] += row[2 * l + 1] * xw.y;
+          for (int l = 0; l < L_ / 2; ++l) {
+            const T2 xv = v2[l], xw = w2[l];
+            av[0] += row[2 * l] * xv.x;
+            av[1] += row[2 * l + 1] * xv.y;
+            aw[0] += row[2 * l] * xw.x;
+            aw[1] += row[2 * l + 1] * xw.y;
+          }
+        } else {  // (odd L: the second vector of a pair starts at an odd element)
+          const T* const v1 = sV + cur * L;
+          const T* const w1 = sW + cur * L;
+#pragma unroll
+          for (int l = 0; l < L_; ++l) {
+            av[l & 1] += row[l] * v1[l];
+            aw[l & 1] += row[l] * w1[l];
+          }
         }
         const T accv = av[0] + av[1] + bcol, accw = aw[0] + aw[1] + bcol * upv;
         if (isA && j < N) {
@@ -2264,6 +2277,7 @@ __device__ __forceinline__ void step_body(const StepArgs<T>& a, const StepVar<T>
       }
       block_sync_lds<TPB>();  // (the last outputs)
     } else if constexpr (ONE_REGION) {
+      static_assert(TPB == 256, "this recursion is the four-wave kernel's: a one-wave one-region set takes the static path above");
       // Four-wave trajectories, y = C x (cfg5 sizes, L = 64): threads 0-127 run the v-chain, 128-255 the w-chain; a PAIR of
       // threads keeps one row of A in registers for the whole recursion, half a row each (32 of the 64 columns: every
       // thread multiplies, and a row costs 64 registers instead of the 128 of one-row-per-thread, which left two of the
