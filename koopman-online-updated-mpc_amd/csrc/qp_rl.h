@@ -447,23 +447,35 @@ __device__ __forceinline__ bool qp_rl(double* const sR, const double* sf, const 
     cs.valid = 0;
     return true;
   }
+  // (default-option kernel: the handle's copies of the warm start, U0, u_store and the state leave with the last step of the launch)
+  bool launch_last = true;
+  if constexpr ((O::LB & (O::LB_WARM | O::LB_OUT)) != 0) launch_last = O::launch_last(sv);
+  const bool warm_out = (O::LB & O::LB_WARM) ? launch_last : true, store_out = (O::LB & O::LB_OUT) ? launch_last : true;
   if (own && !half) {
     if (O::has_useq(a)) io_st<IOT>(a.Useq, (size_t)t * B + b, x);
-    if (O::warm(a)) a.x_warm[(size_t)t * B + b] = x;
+    if constexpr ((O::LB & O::LB_WARM) != 0) {
+      // the warm start of the next solve waits in LDS, where f was (read into registers at the start of this solve, rewritten by the
+      // next step's H / f pass behind the read of this copy); the handle's copy is stored by the last step of the launch
+      lds_st(const_cast<double*>(sf) + t, x);
+      if (warm_out) a.x_warm[(size_t)t * B + b] = x;
+    } else if (O::warm(a)) a.x_warm[(size_t)t * B + b] = x;
   }
   if (tid == 0) {
     const double uout = O::du_mode(a) ? uprev + x : x;  // U0 = U0 + dU*(1)   (Tank_System.m:192)
     *u_slot = x;  // (the first move, for a covariance update done ahead: step_v2.h)
-    if (O::has_u0(sv)) io_st<IOT>(sv.U0, b, uout);
-    if (O::has_u_store(a)) a.u_store[b] = uout;
+    if (O::has_u0(sv) && store_out) io_st<IOT>(sv.U0, b, uout);
+    if (O::has_u_store(a) && store_out) a.u_store[b] = uout;
     if (O::has_plant(a)) {  // x_loc = f_update(0, x_loc, u_loc)   (duffing.py:871)
       double x1, x2;  // (x_next, when given, is the roll-out's LDS slot -- step_body.h lds_ld: as a select of two addresses these were
       // flat loads, which wait for both counters: behind the step's write-back a drain of every outstanding store, K = 20 - 4 %)
       if (sv.x_next) { x1 = lds_ld(sv.x_next); x2 = lds_ld(sv.x_next + 1); }
       else { x1 = io_ld<IOT>(a.X_rw, b); x2 = io_ld<IOT>(a.X_rw, (size_t)B + b); }
       plant_apply<double>(a.plant, sv.plant_switched, a.plant_h, x1, x2, uout);
-      io_st<IOT>(a.X_rw, b, x1);
-      io_st<IOT>(a.X_rw, (size_t)B + b, x2);
+      // (with an LDS slot the next lift and step read x_{k+1} there; without one -- the RBF lift -- the handle's copy carries it)
+      if (store_out || !sv.x_next) {
+        io_st<IOT>(a.X_rw, b, x1);
+        io_st<IOT>(a.X_rw, (size_t)B + b, x2);
+      }
       if (sv.x_next) { lds_st(sv.x_next, x1); lds_st(sv.x_next + 1, x2); }
     }
     if (sv.x_next) {

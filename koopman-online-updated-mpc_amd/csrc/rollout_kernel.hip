@@ -233,7 +233,9 @@ __device__ __attribute__((noinline)) void ro_encoder_tiles(const int wv_, const 
 // OPT: the option set fixed at compile time (step_body.h RoOpt).  RO_OPT_DEFAULT -- the handle a controller created with its defaults
 // launches without a log, DESIGN.md 4.1 -- is the generic kernel without the branches of the other option values; it carries u_{k-1} from
 // step to step in scalar registers.  (Holding further step arguments in scalar registers across the loop was measured group by group and
-// raised the spill count every time: profiles/default_option_kernel.txt, tools/experiments/rollout_held_arguments.h.txt.)
+// raised the spill count every time: profiles/default_option_kernel.txt, tools/experiments/rollout_held_arguments.h.txt.)  Its step loop
+// does not keep the handle's copies of psi, the warm start, U0, u_store and the state current: the last steps of a launch store them
+// (RoOpt::LB, profiles/launch_boundary_state.txt).
 template <int L_, int N_, int Q_, int NW, int KS_, typename IOT = double, bool TERM = false, bool DIAG = false, int OPT = RO_OPT_GENERIC>
 __global__ __launch_bounds__((ro_max_threads<L_, N_, Q_, NW, KS_>())) void rollout_kernel(const RolloutArgs<double> ra) {
   typedef RoOpt<OPT> O;
@@ -563,8 +565,12 @@ __global__ __launch_bounds__((ro_max_threads<L_, N_, Q_, NW, KS_>())) void rollo
       int woff = (O::D ? h_wbase : R.wbase) + wv * (O::D ? h_wstride : R.wstride), bk = b;
       asm volatile("" : "+s"(woff), "+s"(bk));  // (as local_tid: keeps the step's address arithmetic inside the loop)
       double* const wsm = smem + woff;
-      double* const psi_now = R.psi[cur];
-      if (lane < L) psi_now[(size_t)b * L + lane] = psi_i;  // (state of the handle; the step takes psi from the registers)
+      // (state of the handle; the step takes psi from the registers.  Default-option kernel: nothing reads the handle's copies before
+      //  the launch ends, so only the last two steps store -- both ping-pong buffers then end as after a store per step.  Not with the
+      //  RBF lift: (8, 30, 2) spills 96 scalar registers with it, 94 without -- profiles/launch_boundary_state.txt)
+      const bool psi_out = !(O::LB & O::LB_PSI) || RBF || k + 2 >= R.steps;
+      double* const psi_now = psi_out ? R.psi[cur] : nullptr;
+      if (psi_out && lane < L) psi_now[(size_t)b * L + lane] = psi_i;
       V2DiagOut dgo{nullptr, nullptr, nullptr};
       if constexpr (DIAG) {
         if (R.Psi_log && lane < L) io_st<IOT>(R.Psi_log, ((size_t)k * L + lane) * B + b, psi_i);  // (logXLOClift, duffing.py:850)
@@ -585,6 +591,9 @@ __global__ __launch_bounds__((ro_max_threads<L_, N_, Q_, NW, KS_>())) void rollo
       if constexpr (O::D) sv.U0 = a.U0;
       else sv.U0 = R.U_log ? io_at<IOT>(R.U_log, (size_t)k * B) : a.U0;
       if constexpr (O::D) { sv.u_prev_in_regs = k > 0 ? 1 : 0; sv.u_prev_v = u_carry; }
+      // (... and keeps the warm start in LDS between its first and its last step, which is also the only one that stores U0, u_store
+      //  and the state: step_body.h StepVar)
+      if constexpr (O::D) { sv.step_k = k; sv.launch_steps = &R.steps; }
       sv.x_next = RBF ? nullptr : sXn + wv * 4;
       sv.cov_done = (k > 0 && !RO_NO_UPDATE) ? 1 : 0;
       // (waves without an encoder tile do the next step's covariance half inside the next lift instead: see above)

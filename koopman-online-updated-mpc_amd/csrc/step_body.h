@@ -108,6 +108,13 @@ template <typename T> struct StepVar {
   // default-option roll-out (RoOpt below): u_{k-1} comes from the step before in scalar registers instead of StepArgs::u_prev[b]
   int u_prev_in_regs = 0;
   T u_prev_v = T(0);
+  // default-option roll-out: the step's number in the launch and where the launch's step count lies (kernel-argument segment).  The
+  // handle's copies of the warm start, U0, u_store and the state cannot be observed before the launch ends: the first step reads
+  // StepArgs::x_warm, every later one the copy the solve before parked in LDS (qp_rl.h), and only the last step stores them (a solve
+  // handed over to qp_lds stores as ever).  RoOpt::launch_first / launch_last test where they are used: as flags set at the top of the
+  // step they were two more scalar registers alive across it (96 / 97 spilled instead of 95)
+  int step_k = 0;
+  const int __attribute__((address_space(4)))* launch_steps = nullptr;
 };
 
 // Option set of the fused roll-out that is fixed at compile time (template parameter OPT of rollout_kernel, step_v2 and qp_rl).
@@ -133,6 +140,22 @@ template <int OPT> struct RoOpt {
   static __device__ __forceinline__ bool has_u_store(const A& a) { if constexpr (D) return true; else return a.u_store != nullptr; }
   static __device__ __forceinline__ bool has_plant(const A& a) { if constexpr (D) return true; else return a.plant >= 0; }
   template <typename SV> static __device__ __forceinline__ bool has_u0(const SV& sv) { if constexpr (D) return true; else return sv.U0 != nullptr; }
+  // Handle-only state the default-option kernel keeps out of its step loop (profiles/launch_boundary_state.txt measures them one by one):
+  //   LB_PSI   psi_now is stored by the last two steps of a launch only
+  //   LB_WARM  the warm start travels from solve to solve in LDS; StepArgs::x_warm is read by the first step and stored by the last
+  //   LB_OUT   U0, u_store and (where x_{k+1} is carried in an LDS slot) the state are stored by the last step only
+  enum { LB_PSI = 1, LB_WARM = 2, LB_OUT = 4 };
+#ifndef KMPC_RO_LB
+#define KMPC_RO_LB 7
+#endif
+  static constexpr int LB = D ? (KMPC_RO_LB) : 0;
+  // first / last step of a launch (StepVar::step_k, launch_steps)
+  template <typename SV> static __device__ __forceinline__ bool launch_first(const SV& sv) {
+    int k = sv.step_k; asm volatile("" : "+s"(k)); return k == 0;
+  }
+  template <typename SV> static __device__ __forceinline__ bool launch_last(const SV& sv) {
+    int k = sv.step_k; asm volatile("" : "+s"(k)); return k + 1 >= *sv.launch_steps;
+  }
 };
 
 // e = tid, tid + TPB, ... < count.  With a compile-time COUNT the loop is fully unrolled, so that the loads of all

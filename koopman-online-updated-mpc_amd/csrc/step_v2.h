@@ -41,6 +41,7 @@ static constexpr bool step_v2_dims(int L, int N, int q) { return q != L && q > 0
 //   zp   N q     zeros: e_j beyond the horizon (the f lanes of the H / f pass read past the end)             persistent
 //   vec  red 16 | f N | predicted bounds N | e (one q-block in front, N q) ... zp ... | g (N+1) q | dump 64 + (N+1) q
 // (the fall-back solver's vectors alias g and the dump).  Nothing here is overlaid by the lift scratch.
+// (default-option roll-out: between two solves f holds the last minimiser, the next solve's warm start -- qp_rl.h)
 static constexpr int v2_region1(int N) { return (N * rl_stride(N) + 1) & ~1; }  // (padded row stride: qp_rl.h)
 static constexpr int v2_cov_elems(int L) { return 32 + ((L + 1) & ~1); }  // gains of a covariance update done ahead: lanes 0-31, lanes 32 .. 32+L-1
 static constexpr int v2_carry_elems(int L) { return 66 + v2_cov_elems(L); }
@@ -350,7 +351,14 @@ __device__ __forceinline__ void step_v2(const StepArgs<double>& a, const StepVar
     block_sync<64>();
   }
   KTRACE(6);
-  if ((sv.phases & PH_QP) && O::warm(a)) xw_pre = a.x_warm[(size_t)(t < N_ ? t : 0) * a.B + b];
+  if constexpr ((O::LB & O::LB_WARM) != 0) {
+    // (the minimiser the solve before parked in the f vector's place, dead from the start of a solve until the pass below rewrites
+    //  it: qp_rl.h; the first step of a launch reads the handle's copy)
+    if (sv.phases & PH_QP) {
+      if (O::launch_first(sv)) xw_pre = a.x_warm[(size_t)(t < N_ ? t : 0) * a.B + b];
+      else xw_pre = lds_ld(sf + (t < N_ ? t : 0));
+    }
+  } else if ((sv.phases & PH_QP) && O::warm(a)) xw_pre = a.x_warm[(size_t)(t < N_ ? t : 0) * a.B + b];
   // the tableau of the last solve leaves LDS before H takes its place
   double M[N_];
   double rs = 1.0, rsi = 1.0;
@@ -468,6 +476,8 @@ __device__ __forceinline__ void step_v2(const StepArgs<double>& a, const StepVar
       block_sync<64>();
       for (int e = tid; e < N * q; e += 64) sEr[N * q + e] = 0.0;  // (the solver's vectors may have covered the zeros behind e_N)
       if (tid == 0) red[15] = qxo[0];
+      // (default-option kernel: qp_lds stored the handle's copies itself, as ever; the minimiser it left in qxo is parked for the next step)
+      if constexpr ((O::LB & O::LB_WARM) != 0) { if (tid < N) lds_st(sf + tid, lds_ld(qxo + tid)); }
     }
     if (!half) {
       sCs[t] = rs;
