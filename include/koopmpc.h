@@ -345,6 +345,10 @@ int kmpc_rollout_is_fused(const kmpc_handle* h);
  * generic kernel, 2 the fused default-option kernel -- the instantiation for handles created with the default options and
  * rolled out without a log; same results either way                                              */
 int kmpc_rollout_variant(const kmpc_handle* h);
+/* what that launch kept resident in LDS of the encoder's operands (the default-option kernel of (20, 20, 2) only): a
+ * mask, 1 the biases of the hidden and output layers, 2 output tile 0; 0 for every other launch.  *lds_bytes (may be null) receives the
+ * dynamic LDS the launch asked for (0 where a plug-in or the float32 panels launched)                              */
+int kmpc_rollout_resident(const kmpc_handle* h, int* lds_bytes);
 /* Where that kernel comes from.  The reference's dimensions are constants edited in its scripts (duffing.py:66 Nlift, :632-633
  * MPCHorizon; Koopman_update.m:67, 70, 113: L = 10, N = 10), so the fused roll-out is not tied to a list: libkoopmpc.so holds the
  * instantiations of the BASELINE / reference dimension sets, and kmpc_create makes the kernel of any other set as a PLUG-IN --

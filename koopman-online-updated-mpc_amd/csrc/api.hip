@@ -35,6 +35,7 @@ struct kmpc_handle {
   // the route the last kmpc_rollout with steps > 0 took: 0 per-step launches (or no roll-out yet), 1 the fused generic kernel, 2 the
   // fused default-option kernel (csrc/step_body.h RoOpt)
   int last_rollout_variant = 0;
+  int last_rollout_resident = 0, last_rollout_lds = 0;  // kmpc_rollout_resident
   virtual int rollout_plugin_status(std::string* text) const = 0;
   virtual int reset(hipStream_t s) = 0;
   virtual int state_init(double P0, double barQ0, hipStream_t s) = 0;
@@ -1320,10 +1321,13 @@ struct Impl : kmpc_handle {
     }
     if (steps > 0 && fused) {
       const int rcf = rollout_fused(ctx, plant, X, ref, rpt, steps, step0, switch_step, hs, Ulog, Xlog, st, it, s);
-      if (!rcf) last_rollout_variant = rollout_last_variant();
+      if (!rcf) {
+        last_rollout_variant = rollout_last_variant();
+        last_rollout_resident = rollout_last_resident(&last_rollout_lds);
+      }
       return rcf;
     }
-    if (steps > 0) last_rollout_variant = 0;
+    if (steps > 0) last_rollout_variant = last_rollout_resident = last_rollout_lds = 0;
     if (steps == 0 && fused) {
       // a call without steps brings the handle into the form the fused roll-out works on (the wave image of a state that was
       // set, restored or stepped through the dense blocks): set-up that the next kmpc_rollout would otherwise pay
@@ -1876,6 +1880,11 @@ int kmpc_solve_dare(const void* A, const void* B, const double* Q, double R, int
 int kmpc_set_terminal_refresh(kmpc_handle* h, int every, const double* Q, double R, int maxiter, double eps) { NN(h); return h->set_terminal_refresh(every, Q, R, maxiter, eps); }
 int kmpc_rollout_is_fused(const kmpc_handle* h) { NN(h); return h->rollout_is_fused(); }
 int kmpc_rollout_variant(const kmpc_handle* h) { NN(h); return h->last_rollout_variant; }
+int kmpc_rollout_resident(const kmpc_handle* h, int* lds_bytes) {
+  NN(h);
+  if (lds_bytes) *lds_bytes = h->last_rollout_lds;
+  return h->last_rollout_resident;
+}
 // Makes (or finds) the plug-in a handle of this configuration would load -- no device needed: hipcc cross-compiles.  For builds that
 // want the kernel cache filled before the first kmpc_create (__graft_entry__.build(), an installer, the first rank of a node).
 static void put_text(char* text, int text_bytes, const std::string& t) { if (text && text_bytes > 0) snprintf(text, (size_t)text_bytes, "%s", t.c_str()); }

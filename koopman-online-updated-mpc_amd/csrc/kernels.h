@@ -19,6 +19,7 @@ namespace kmpc {
 //   KMPC_SHARED_MODEL_R3      round-3 model kernel (eight waves)          KMPC_SHARED_LIFT_GRAM_2  lift and Gram sums as two launches
 //   KMPC_SHARED_NO_FAST       every trajectory through the QP kernel      KMPC_SHARED_NO_LIST      solve-only kernel: one workgroup per trajectory
 //   KMPC_ROLLOUT_GENERIC      the fused roll-out never takes its default-option kernel (rollout_kernel.hip; read once per process)
+//   KMPC_ROLLOUT_RESIDENT=0|2 parts of the encoder's LDS-resident operand area beside the biases (2: output tile 0, the default; once per process)
 const char* dbg_env(const char* name);
 
 
@@ -125,6 +126,11 @@ template <typename T> struct RolloutArgs {
   int wstride;              // per-wave LDS region in elements
   int wbase;                // LDS offset (elements) of the first per-wave region (register-state step: behind the lift scratch)
   int keep_off;             // LDS offset (elements) of the part the lift scratch does not overlay
+  // launch-resident encoder operands (default-option (20, 20, 2) kernel, rollout_kernel.hip RO_RES_*): LDS offset (elements) of the area
+  // behind the x slots, 0: no area (every launch of another kernel; the launcher gives this kernel no launch without one); res_parts:
+  // which operands the launcher's plan put there (RO_RES_BIAS always, RO_RES_TILE0 if the LDS reaches: what is
+  // not there stays on the global path)
+  int res_off, res_parts;
   T* U_log; T* X_log;       // optional (steps x B), (steps x n x B)
   // register-state step (step_v2.h): the wave images of the trajectories' state, [B][img_stride]
   T* img; long img_stride;
@@ -204,7 +210,7 @@ hipError_t launch_dare(const DareArgs& a, hipStream_t s);
 size_t step_lds_bytes(int n, int L, int q, int N, size_t elem, int* r1, int* r2, bool lds_tableau = true);
 
 // layout version of StepArgs / RolloutArgs as the roll-out plug-ins see them (rollout_jit.hip): bump with any change of the two structs
-#define KMPC_PLUGIN_ABI 6003
+#define KMPC_PLUGIN_ABI 6004
 template <typename T> hipError_t launch_step(const StepArgs<T>& a, int threads, hipStream_t s);
 // true if (T, n, L, N, q, threads, lift kind) has a fused roll-out instantiation that fits in LDS
 template <typename T> bool rollout_fused_available(int n, int L, int N, int q, int threads, bool rbf);
@@ -226,6 +232,8 @@ template <typename T> hipError_t launch_rollout_fused(const RolloutArgs<T>& a, h
 // which kernel the last launch_rollout_fused of the calling thread ran: 1 the generic one (built-in or plug-in), 2 the default-option
 // instantiation (step_body.h RoOpt: every option of the launch had the value that kernel fixes)
 int rollout_last_variant();
+// the RO_RES_* parts the last roll-out launch of this thread kept resident in LDS (0: none) and the dynamic LDS bytes it asked for
+int rollout_last_resident(int* lds_bytes);
 bool rollout_builtin(int L, int N, int q, bool io32);  // libkoopmpc.so itself holds the instantiations of this set
 // the plug-in a launch of this configuration needs; false: none (built-in set, or the set does not fit the fused kernel at all)
 // (term: the variant with the per-step terminal refresh -- always a plug-in, also for the built-in sets; diag: the variant with the

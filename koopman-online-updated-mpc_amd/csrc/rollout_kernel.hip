@@ -129,11 +129,41 @@ template <int L_, int N_, int Q_> constexpr bool ro_encoder_call() { return N_ >
 // across the lift sit in the preserved ones), and the window is 1.5 - 2.5 % shorter at K = 20, 3.5 - 4 % at K = 200
 // (profiles/r6_cfg2_lift_ksplit.txt).  The arguments arrive in vector registers: the wave-uniform ones go back to scalar registers, the
 // pointers to their address spaces (generic pointers are flat loads, which wait for both counters).
-template <int KS_, int NW>
+//
+// RESIDENT MODE (RES; the default-option kernel of (20, 20, 2): sixteen waves, KS = 25, Hp = 112, Lp = 32).  What the encoder reads that is the
+// same for every step of a launch and small enough sits in an LDS area behind the x slots, filled once per launch (ro_fill_resident):
+//   [ bh0: 112 ][ bh1: 112 ][ bo: 32 ][ output tile 0 as packed: 25 k-steps x 64 lanes ]
+// The bias accumulators of every layer are LDS reads behind the barrier instead of a round trip to L2 in front of the layer's first product,
+// and wave 0's A operands of the output layer are LDS reads instead of 25 fragments from L2 per step.  Same MFMA, same operand values in
+// the same order: psi is bit for bit the non-resident one.  RolloutArgs::res_parts says which operands the launcher's plan put there; an
+// output tile that is not keeps the global path, prefetch across the barrier included.  Output tile 1 (rows 16-19 of psi and twelve zero
+// rows) always does: a compact resident copy of its four real rows, read under a lane mask, was built and measured SLOWER than the global
+// path (profiles/encoder_resident_operands.txt) and is not in the code.
+constexpr int RO_RES_BH1 = 112, RO_RES_BO = 224, RO_RES_T0 = 256, RO_RES_ELEMS = RO_RES_T0 + 25 * 64;
+enum { RO_RES_BIAS = 1, RO_RES_TILE0 = 2 };
+template <bool RES> struct RoRes {};  // (non-resident: an empty argument, the function's signature is what it was)
+// (ONE register: with the nineteen arguments in front of it a second one would travel on the stack)
+template <> struct RoRes<true> { int off_parts; };  // RolloutArgs::res_off | res_parts << 16
+// the whole workgroup copies the plan's operands into the area (the barrier in front of the step loop waits for it)
+__device__ __attribute__((noinline)) void ro_fill_resident(double* area_, int parts, int nhh, const double* bh0, const double* bh1, const double* bo, const double* Wop,
+                                                 int tid, int threads) {
+  double __attribute__((address_space(3)))* const area = (double __attribute__((address_space(3)))*)area_;
+  for (int i = tid; i < RO_RES_T0; i += threads) {
+    double v = 0.0;
+    if (i < RO_RES_BH1) { if (nhh > 0) v = bh0[i]; }
+    else if (i < RO_RES_BO) { if (nhh > 1) v = bh1[i - RO_RES_BH1]; }
+    else v = bo[i - RO_RES_BO];
+    area[i] = v;
+  }
+  if (parts & RO_RES_TILE0)
+    for (int i = tid; i < 25 * 64; i += threads) area[RO_RES_T0 + i] = Wop[i];
+}
+template <int KS_, int NW, bool RES = false>
 __device__ __attribute__((noinline)) void ro_encoder_tiles(const int wv_, const int lane, const int b0_, const int KSr_, const bool hid_, const bool out_, const int nhh_,
                                                         const double* W1_, const double* b1_, const double* Wh0_, const double* Wh1_, const double* Wo_,
                                                         const double* bh0_, const double* bh1_, const double* bo_, const double* sXn_, double* sAct0_,
-                                                        double* sAct1_, double* sPsi_) {
+                                                        double* sAct1_, double* sPsi_, const RoRes<RES> res_ = {}) {
+  static_assert(!RES || (KS_ == 25 && NW == 16), "resident operands: the layout is that of KS = 25, sixteen waves");
   typedef double d4_t __attribute__((ext_vector_type(4)));
   typedef const double __attribute__((address_space(1))) * gp_t;
   typedef double __attribute__((address_space(3))) * lp_t;
@@ -180,6 +210,97 @@ __device__ __attribute__((noinline)) void ro_encoder_tiles(const int wv_, const 
   LSTAMP(1);
   __syncthreads();
   LSTAMP(2);
+  if constexpr (RES) {
+    // ---- resident mode: the same layers with the bias accumulators, and where the plan has them the output layer's A operands, from the
+    //      area.  The output layer stands behind the loop over the hidden layers, not in it: what its LDS path needs is not alive across
+    //      the hidden layers, and the function stays within the call-clobbered registers.
+    const lp_t sRes = sAct0 + (uni(res_.off_parts) & 0xffff);  // (sAct0 is the base of the workgroup's LDS)
+    const bool outr = out && wv == 0 && ((uni(res_.off_parts) >> 16) & RO_RES_TILE0) != 0;  // this wave's output tile is in the area
+    const bool outg = out && !outr;                                                    // ... is fetched as without the area
+    // the products of one tile over the full K range from fragments in global memory (the first batch is in af[0])
+    // (the lane's activation address in ONE register, opaque: every read of a layer is an immediate offset from it -- otherwise the choice
+    //  between the two activation sets is made again, in scalar registers, in front of every read)
+    auto lane_act = [&](const lp_t act) {
+      lp_t actl = act + bl;
+      asm volatile("" : "+v"(actl));
+      return actl;
+    };
+    auto products_global = [&](const gp_t Wp, const lp_t act, d4_t& acc0, d4_t& acc1) {
+      const lp_t actl = lane_act(act);
+#pragma unroll
+      for (int bt = 0; bt < 32 / RO_KB2; ++bt) {
+        const int kb = bt * RO_KB2;
+        if (kb + RO_KB2 < KS) loadf(Wp, kb + RO_KB2, af[(bt + 1) & 1]);
+#pragma unroll
+        for (int i = 0; i < RO_KB2; i += 2) {
+          if (kb + i < KS) acc0 = __builtin_amdgcn_mfma_f64_16x16x4f64(af[bt & 1][i], actl[(kb + i) * AR], acc0, 0, 0, 0);
+          if (kb + i + 1 < KS) acc1 = __builtin_amdgcn_mfma_f64_16x16x4f64(af[bt & 1][i + 1], actl[(kb + i + 1) * AR], acc1, 0, 0, 0);
+        }
+      }
+    };
+    // ... from the packed copy in the area (ap: this lane's element of k-step 0): batches of RB k-steps in two buffers, one batch ahead (an
+    // LDS read is back within one product), the reads immediate offsets from ap
+    auto products_area = [&](const lp_t ap, const lp_t act, d4_t& acc0, d4_t& acc1) {
+      constexpr int RB = 4;
+      const lp_t actl = lane_act(act);
+      double ar[2][RB];
+      auto loadr = [&](int ks0, double (&dst)[RB]) {
+#pragma unroll
+        for (int i = 0; i < RB; ++i) dst[i] = ks0 + i < KS ? ap[(ks0 + i) * 64] : 0.0;
+      };
+      loadr(0, ar[0]);
+#pragma unroll
+      for (int bt = 0; bt < 32 / RB; ++bt) {
+        const int kb = bt * RB;
+        if (kb + RB < KS) loadr(kb + RB, ar[(bt + 1) & 1]);
+#pragma unroll
+        for (int i = 0; i < RB; i += 2) {
+          if (kb + i < KS) acc0 = __builtin_amdgcn_mfma_f64_16x16x4f64(ar[bt & 1][i], actl[(kb + i) * AR], acc0, 0, 0, 0);
+          if (kb + i + 1 < KS) acc1 = __builtin_amdgcn_mfma_f64_16x16x4f64(ar[bt & 1][i + 1], actl[(kb + i + 1) * AR], acc1, 0, 0, 0);
+        }
+        // (no read of a later batch moves up across this point: with every LDS read of the layer hoisted to its head the function would
+        //  need the preserved registers, and a stack to save them)
+        __builtin_amdgcn_sched_barrier(0);
+      }
+    };
+    for (int h = 0; h < nhh; ++h) {
+      const lp_t act = (h & 1) ? sAct1 : sAct0;
+      const lp_t actn = (h & 1) ? sAct0 : sAct1;
+      if (hid) {
+        const lp_t rbias = sRes + ((h & 1) ? RO_RES_BH1 : 0);
+        d4_t acc0, acc1 = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+        for (int r = 0; r < 4; ++r) acc0[r] = rbias[16 * wv + (lane >> 4) + 4 * r];
+        products_global((h & 1) ? Wh1 : Wh0, act, acc0, acc1);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int row = 16 * wv + (lane >> 4) + 4 * r;
+          const double v = acc0[r] + acc1[r];
+          actn[(row >> 2) * AR + (row & 3) * (AR / 4) + (lane & 15)] = v > 0.0 ? v : 0.0;
+        }
+      }
+      // the next layer's first fragments travel across the barrier (not those of an output tile in the area)
+      if (h + 1 < nhh) { if (hid) loadf(((h + 1) & 1) ? Wh1 : Wh0, 0, af[0]); }
+      else if (outg) loadf(Wo, 0, af[0]);
+      LSTAMP(3 + 2 * h);
+      __syncthreads();
+      LSTAMP(4 + 2 * h);
+    }
+    if (out) {
+      const lp_t act = (nhh & 1) ? sAct1 : sAct0;
+      d4_t acc0, acc1 = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+      for (int r = 0; r < 4; ++r) acc0[r] = sRes[RO_RES_BO + 16 * wv + (lane >> 4) + 4 * r];
+      if (outg) products_global(Wo, act, acc0, acc1);
+      else products_area(sRes + RO_RES_T0 + lane, act, acc0, acc1);
+#pragma unroll
+      for (int r = 0; r < 4; ++r) sPsi[(16 * wv + (lane >> 4) + 4 * r) * 16 + (lane & 15)] = acc0[r] + acc1[r];
+    }
+    LSTAMP(3 + 2 * nhh);
+    __syncthreads();  // (psi is outside the overlay, the waves go their own way)
+    LSTAMP(4 + 2 * nhh);
+    return;
+  }
   // ---- hidden -> hidden layers, then the output layer, all as: tile = wave, full K
   for (int h = 0; h <= nhh; ++h) {
     const bool last = h == nhh;
@@ -279,6 +400,11 @@ __global__ __launch_bounds__((ro_max_threads<L_, N_, Q_, NW, KS_>())) void rollo
   const int b = b0 + slot_traj;
   const bool live = b < B;
   if (!RBF && tid0 < 4 * NC) sXn[tid0] = 0.0;  // (columns of trajectories this workgroup does not have)
+  // the encoder's launch-resident operands (ro_encoder_tiles' resident mode): filled here, once per launch, by every wave of the workgroup
+  constexpr bool RES = O::D && !RBF && NW == 16 && KS_ == 25 && ro_encoder_call<L_, N_, Q_>();
+  if constexpr (RES) {
+    ro_fill_resident(smem + ra.res_off, ra.res_parts, ra.nhh, ra.bh[0], ra.bh[1], ra.bo, ra.Wop, tid0, 64 * NW);
+  }
   __syncthreads();
   if (!RBF && (tid0 & 63) < 4)
     sXn[wave * 4 + (tid0 & 63)] = (live && (int)(tid0 & 63) < n) ? io_ld<IOT>(ra.s.X_rw, (size_t)(tid0 & 63) * B + b) : 0.0;
@@ -470,7 +596,13 @@ __global__ __launch_bounds__((ro_max_threads<L_, N_, Q_, NW, KS_>())) void rollo
         for (int i = 0; i < R.nhh; ++i) __syncthreads();
       } else if constexpr (ro_encoder_call<L_, N_, Q_>()) {
         // the tile waves: the products of all layers (ro_encoder_tiles, a function of its own)
-        ro_encoder_tiles<KS_, NW>(wv, lane, b0, KS, hid, out, R.nhh, R.W1, R.b1, R.Whp[0], R.Whp[1], R.Wop, R.bh[0], R.bh[1], R.bo, sXn, sAct0, sAct1, sPsi);
+        // (resident mode has ONE call site: with a second one for a launch without an area the kernel spills 100 scalar registers and a
+        //  vector one.  The launcher plans at least the biases for every launch of this kernel: launch_rollout_impl)
+        if constexpr (RES)
+          ro_encoder_tiles<KS_, NW, true>(wv, lane, b0, KS, hid, out, R.nhh, R.W1, R.b1, R.Whp[0], R.Whp[1], R.Wop, nullptr, nullptr, nullptr, sXn, sAct0, sAct1, sPsi,
+                                          RoRes<true>{R.res_off | (R.res_parts << 16)});
+        else
+          ro_encoder_tiles<KS_, NW>(wv, lane, b0, KS, hid, out, R.nhh, R.W1, R.b1, R.Whp[0], R.Whp[1], R.Wop, R.bh[0], R.bh[1], R.bo, sXn, sAct0, sAct1, sPsi);
       } else {
       // (the same products inline -- the short-horizon sets, see ro_encoder_call)
       constexpr int AR = NW == 8 ? 32 : 64;
@@ -798,6 +930,31 @@ template <int L_, int N_, int Q_> constexpr bool ro_default_built() {
   return Q_ == 2 && ((L_ == 20 && N_ == 20) || (L_ == 8 && N_ == 30));
 #endif
 }
+// The launch-resident encoder operands of the default-option (20, 20, 2) launch (ro_encoder_tiles' resident mode): an area behind the x slots,
+// planned here once per launch -- the biases, then output tile 0, each if it ends below 160 KiB; what does not stays on the global path.
+// Returns the elements the launch asks for.  The kernel reads its biases from the area unconditionally (ONE call site of the encoder), so a
+// launch WITHOUT an area (res_off = 0) must never reach it: launch_rollout_impl sends it to the generic kernel.  At the one set that has
+// the kernel this cannot happen -- 18 208 + 256 <= 20 480, the static_assert there -- and both parts fit: 18 208 + 1 856 = 20 064 elements =
+// 160 512 B.
+static size_t ro_resident_plan(RolloutArgs<double>& k, size_t elems) {
+  static const char* env = dbg_env("KMPC_ROLLOUT_RESIDENT");  // measurement / test aid: a mask of the RO_RES_* parts allowed (the biases always are)
+  const int allowed = env ? atoi(env) : RO_RES_TILE0;
+  const size_t cap = 160 * 1024 / sizeof(double), off = (elems + 1) & ~(size_t)1;  // (16-byte aligned)
+  k.res_off = k.res_parts = 0;
+  if (k.Lp != 32 || k.Hp != 112 || k.KS != 25 || off + RO_RES_T0 > cap) return elems;
+  k.res_off = (int)off;
+  k.res_parts = RO_RES_BIAS;
+  if ((allowed & RO_RES_TILE0) && off + RO_RES_ELEMS <= cap) { k.res_parts |= RO_RES_TILE0; return off + RO_RES_ELEMS; }
+  return off + RO_RES_T0;
+}
+// what the last roll-out launch of this thread asked for: dynamic LDS bytes, and the RO_RES_* parts its plan put into the area (0: no area)
+static thread_local int g_rollout_last_lds = 0, g_rollout_last_res_parts = 0;
+#if !defined(KMPC_ROLLOUT_JIT_TU) && !defined(KMPC_ROLLOUT_IO32_TU)
+int rollout_last_resident(int* lds_bytes) {
+  if (lds_bytes) *lds_bytes = g_rollout_last_lds;
+  return g_rollout_last_res_parts;
+}
+#endif
 template <int L_, int N_, int Q_, typename IOT = double> static hipError_t launch_rollout_impl(const RolloutArgs<double>& a, hipStream_t s, int waves_in = 0) {
   RolloutArgs<double> k = a;
   const bool rbf = a.lift_rbf != 0;
@@ -838,13 +995,27 @@ template <int L_, int N_, int Q_, typename IOT = double> static hipError_t launc
 #else
   if (rbf && a.rbf_matlab > 1) return hipErrorInvalidValue;  // (rbf.m's other kinds are always plug-ins: launch_rollout_fused)
   g_rollout_last_variant = 1;
+  g_rollout_last_lds = (int)lds;
+  g_rollout_last_res_parts = 0;
   if constexpr (sizeof(IOT) == 8 && ro_default_built<L_, N_, Q_>()) {
     static const bool generic = dbg_env("KMPC_ROLLOUT_GENERIC") != nullptr;  // measurement / test aid: the generic kernel for every launch
     // ((20, 20, 2): the MLP lift, sixteen waves, the reference's encoder width; (8, 30, 2): the RBF lift)
-    if (!generic && rollout_default_options(a) && (L_ == 20 ? (!rbf && waves == 16 && ks25) : rbf)) {
+    bool dflt = !generic && rollout_default_options(a) && (L_ == 20 ? (!rbf && waves == 16 && ks25) : rbf);
+    size_t lds_d = lds;
+    if constexpr (L_ == 20) {  // (with the encoder's resident operands: k.res_off, k.res_parts)
+      static_assert(ro_scratch() + 16 * v2_lds_elems(20, 2, 20) + 32 * 16 + 4 * 16 + RO_RES_T0 <= 160 * 1024 / sizeof(double),
+                    "the resident kernel reads its biases from the area: they must fit behind the x slots of this set");
+      if (dflt) {
+        lds_d = ro_resident_plan(k, elems) * sizeof(double);
+        dflt = k.res_off != 0;
+      }
+    }
+    if (dflt) {
       g_rollout_last_variant = 2;
-      if constexpr (L_ == 20) return launch_rollout_nw<L_, N_, Q_, 16, 25, IOT, false, false, RO_OPT_DEFAULT>(k, waves, lds, s);
-      else return launch_rollout_nw<L_, N_, Q_, 16, -1, IOT, false, false, RO_OPT_DEFAULT>(k, waves, lds, s);
+      g_rollout_last_lds = (int)lds_d;
+      g_rollout_last_res_parts = k.res_parts;
+      if constexpr (L_ == 20) return launch_rollout_nw<L_, N_, Q_, 16, 25, IOT, false, false, RO_OPT_DEFAULT>(k, waves, lds_d, s);
+      else return launch_rollout_nw<L_, N_, Q_, 16, -1, IOT, false, false, RO_OPT_DEFAULT>(k, waves, lds_d, s);
     }
   }
   if (rbf) return launch_rollout_nw<L_, N_, Q_, 16, -1, IOT>(k, waves, lds, s);
@@ -955,6 +1126,7 @@ template <> hipError_t launch_rollout_fused<double>(const RolloutArgs<double>& a
   if (a.s.B <= 0 || a.steps <= 0) return hipSuccess;
   if (!a.lift_rbf && (a.Hp > 128 || (a.Hp & 15) || a.Lp > 64 || a.KS > 32 || a.nhh < 0 || a.nhh > 2 || a.s.n > 4))
     return hipErrorInvalidValue;
+  g_rollout_last_lds = g_rollout_last_res_parts = 0;  // (plug-ins and the float32 panels: no resident operands, LDS not reported)
   if (a.term_every > 0 || a.diag || (a.lift_rbf && a.rbf_matlab > 1) || !rollout_builtin(a.s.L, a.s.N, a.s.q, a.io_f32 != 0)) return launch_rollout_plugin(a, plugin, s);
   if (a.io_f32) { g_rollout_last_variant = 1; return launch_rollout_io32(a, s); }
   using IOT = double;

@@ -54,6 +54,7 @@ SIGNATURES = {
     "kmpc_set_terminal_refresh": (_I, [_VP, _I, _DP, _D, _I, _D]),
     "kmpc_rollout_is_fused": (_I, [_VP]),
     "kmpc_rollout_variant": (_I, [_VP]),
+    "kmpc_rollout_resident": (_I, [_VP, _VP]),
     "kmpc_rollout_plugin_status": (_I, [_VP, C.c_char_p, _I]),
     "kmpc_rollout_plugin_prebuild": (_I, [_I, _I, _I, _I, _I, _I, _I, _I, C.c_char_p, _I]),
     "kmpc_set_rollout_workgroup": (_I, [_I]),

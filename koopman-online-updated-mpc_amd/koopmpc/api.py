@@ -657,6 +657,13 @@ class KoopmanMPC:
         2 the fused default-option kernel (a controller created with the default options, rolled out without a log)."""
         return int(self.lib.kmpc_rollout_variant(self.h))
 
+    def rollout_resident(self):
+        """(parts, lds_bytes) of the last rollout() with steps > 0: which encoder operands the launch kept resident in LDS (a mask: 1 the
+        biases, 2 output tile 0; 0 for every launch but the default-option kernel's at (20, 20, 2)) and the dynamic LDS it asked for."""
+        lds = C.c_int(0)
+        parts = int(self.lib.kmpc_rollout_resident(self.h, C.byref(lds)))
+        return parts, int(lds.value)
+
     def rollout_plugin_status(self):
         """(code, text): where the fused roll-out kernel of this controller comes from -- 0 the library's own instantiation, 1 a
         plug-in made for this dimension set when the controller was created (text: its file, found in the kernel cache or compiled
