@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "../../include/koopmpc.h"
+#include "devbuf.h"
 #include "kernels.h"
 #include <dlfcn.h>
 #include <rccl/rccl.h>  // types and enumerators only (ncclDouble, ncclSum): the library resolves ncclAllReduce at run time
@@ -163,13 +164,6 @@ static inline bool plant_id_ok(int plant) {
   return base >= KMPC_PLANT_DUFFING && base <= KMPC_PLANT_TANK && !(base == KMPC_PLANT_TANK && (plant & KMPC_PLANT_RK4_MATLAB));
 }
 
-// a device temporary that is freed on every return path (the HIPCHK macro returns from the middle of a function)
-struct DevTmp {
-  void* p = nullptr;
-  ~DevTmp() { if (p) (void)hipFree(p); }
-  template <typename U> U* as() const { return static_cast<U*>(p); }
-};
-
 // What a caller hands down to the step / solve / roll-out bodies of a handle (nothing of it is kept in the handle).  The default is a plain
 // call: kmpc_step, kmpc_shared_solve, kmpc_rollout.
 struct DiagLogs { void *Psi, *dA, *dB, *dC; };  // the logs of a kmpc_rollout_diag call (RolloutArgs::Psi_log ...), any may be null
@@ -181,6 +175,47 @@ struct StepCtx {
   const DiagLogs* diag = nullptr;  // the call is a kmpc_rollout_diag
 };
 
+// ---- The state blob of kmpc_state_export / kmpc_state_import, version 2.  This comment is the format; Impl::sections() is its one
+// implementation and tests/test_gpu_state_blob_layout.py holds the bytes to it.  Everything is native-endian and packed back to back,
+// without alignment between sections.  T is the handle's dtype (float or double), p = L + 1, q the number of output rows,
+// even_up(v) = v rounded up to an even number.
+//
+//   header    BlobHeader, 80 bytes: 16 int32 in the order of the struct, then the float64 scales P0, barQ0 of the estimator's restart.
+//             dtype is KMPC_F32 / KMPC_F64; the flags are 0 or 1; wterm_blocks is 0 without a terminal section, B with
+//             wterm_from_dare and wterm_per_traj, else 1; reserved is 0.
+//   P         [B][sP] T   inv_K_G of every trajectory: p x p row-major at the head of a stride of sP = even_up(p p) elements
+//   K         [B][sK] T   [A B]: L x p row-major, sK = even_up(L p)
+//   Q         [B][sQ] T   bar_Q: L x L row-major, sQ = even_up(L L)
+//   C         [B][sC] T   n x L row-major, sC = even_up(n L)   (unused for y = psi)
+//   psi_prev  [B][L]  T   psi(x_{k-1})
+//   warm      [N][B]  T   the last minimiser, the start of the next solve
+//   u_prev    [B]     T   u_{k-1}
+//   -- with has_shared:
+//   Gram      [(p + L + n) p] float64   the Gram sums of the shared model
+//   shared K  [L p] T, shared C [n L] T
+//   -- with have_wterm:
+//   terminal  [wterm_blocks][q q]   PN - Qw I, as T; as float64 with wterm_from_dare (the blocks of the Riccati iteration)
+//
+// The content of the stride padding (the odd element of sP .. sC) is no part of the format.
+static constexpr int32_t kBlobMagic = 0x4b4d5043;
+struct BlobHeader {
+  int32_t magic, version, dtype, n, L, N, B, have_prev, rls_fresh;
+  int32_t has_shared, shared_has_samples, have_wterm, wterm_from_dare, wterm_per_traj, wterm_blocks, reserved;
+  double P0, barQ0;
+};
+static_assert(sizeof(BlobHeader) == 80, "BlobHeader is the first 80 bytes of a state blob");
+// one section of a blob as a handle holds it, and the ordered list of them (Impl::sections)
+struct Section {
+  void* ptr; size_t elem, count;  // element size, elements
+  size_t bytes() const { return elem * count; }
+};
+struct Sections {
+  Section s[11];
+  int n = 0, n_traj = 0;  // n_traj: the leading sections that hold per-trajectory state (P .. u_prev)
+  void add(void* ptr, size_t elem, size_t count) { s[n++] = Section{ptr, elem, count}; }
+  int64_t blob_bytes() const { int64_t b = sizeof(BlobHeader); for (int i = 0; i < n; ++i) b += (int64_t)s[i].bytes(); return b; }
+};
+
 template <typename T>
 struct Impl : kmpc_handle {
   int n, m, L, p, q, N, B, threads;
@@ -189,15 +224,15 @@ struct Impl : kmpc_handle {
   std::vector<std::vector<double>> hostW, hostb;  // the layers as given (row-major), kept for finalize_encoder
   long sP, sK, sQ, sC;
   // persistent state
-  T *dP = nullptr, *dK = nullptr, *dQ = nullptr, *dC = nullptr;
-  T *dPsi[2] = {nullptr, nullptr};  // [B][L] trajectory-major: [cur], [prev]
-  T* dUprev = nullptr;
-  T* dQpScr = nullptr;  // [B][N*N] fall-back tableau of the register QP solvers (global scratch, rarely touched)
-  int qp_scr_cap = 0;
+  // (every device block of the handle is a DevBuf, csrc/devbuf.h: freed with the handle, no list to keep)
+  DevBuf<T> dP, dK, dQ, dC;
+  DevBuf<T> dPsi[2];  // [B][L] trajectory-major: [cur], [prev]
+  DevBuf<T> dUprev;
+  DevBuf<T> dQpScr;  // [batch][N*N] fall-back tableau of the register QP solvers (global scratch, rarely touched); grown by kmpc_qp_solve
   // Register-state step (step_v2.h): the fused roll-out of the small y = C x dimension sets streams the state as a "wave image"
   // ([B][sImg] doubles).  The dense blocks above stay the form every other entry point works on; whichever of the two was
   // written last is the valid one and the other is rebuilt on demand (state_to_image / image_to_state, one pass over the state).
-  double* dImg = nullptr;
+  DevBuf<double> dImg;
   long sImg = 0;
   bool use_img = false, img_valid = false, dense_valid = true;
   // KMPC_F32 handle of a register-state dimension set (row g2: BASELINE configs[1] names fp32; SURVEY G6: fp32 panels, float64
@@ -238,15 +273,14 @@ struct Impl : kmpc_handle {
   bool fused_kind_ok() const { return (q == L) == (cfg.output_kind == KMPC_OUT_LIFT); }
   // four-wave solver (threads = 256, float64): every trajectory's last tableau and its variable set, kept from step to step
   // (StepArgs::qp_carry); any change of the model from outside forgets them (the next solve starts from 2H)
-  T* dQpCarry = nullptr;
-  int32_t* dQpCarrySet = nullptr;
-  T* dWarm = nullptr;  // [N][B] last minimiser = start of the next solve (the reference restarts at zeros, duffing.py:634-635)
+  DevBuf<T> dQpCarry;
+  DevBuf<int32_t> dQpCarrySet;
+  DevBuf<T> dWarm;  // [N][B] last minimiser = start of the next solve (the reference restarts at zeros, duffing.py:634-635)
   int cur = 0;
   bool have_prev = false;  // a previous (psi, u) exists -> next step runs the RLS update
   bool rls_fresh = true;   // next RLS update starts from K_A = 0, bar_X = 0
   // parameters
-  T *dW1 = nullptr, *db1 = nullptr, *dWh[2] = {nullptr, nullptr}, *dbh[2] = {nullptr, nullptr}, *dWo = nullptr,
-    *dbo = nullptr, *dcx = nullptr, *dTmp = nullptr;
+  DevBuf<T> dW1, db1, dWh[2], dbh[2], dWo, dbo, dcx, dTmp;
   std::vector<bool> layer_set;
   bool centres_set = false;
   int rbf_k = 1;  // polyharmonic coefficient (rbf.m:15-17), kmpc_set_rbf_order
@@ -283,26 +317,23 @@ struct Impl : kmpc_handle {
     int r1, r2;
     if (step_lds_bytes(n, L, q, N, sizeof(T), &r1, &r2) > 160 * 1024) FAIL(-2, "configuration exceeds 160 KB of LDS");
     sP = even_up((long)p * p); sK = even_up((long)L * p); sQ = even_up((long)L * L); sC = even_up((long)n * L);
-    HIPCHK(hipMalloc(&dP, sizeof(T) * sP * B));
-    HIPCHK(hipMalloc(&dK, sizeof(T) * sK * B));
-    HIPCHK(hipMalloc(&dQ, sizeof(T) * sQ * B));
-    HIPCHK(hipMalloc(&dC, sizeof(T) * sC * B));
-    HIPCHK(hipMalloc(&dPsi[0], sizeof(T) * (size_t)L * B));
-    HIPCHK(hipMalloc(&dPsi[1], sizeof(T) * (size_t)L * B));
-    HIPCHK(hipMalloc(&dUprev, sizeof(T) * (size_t)B));
-    HIPCHK(hipMalloc(&dQpScr, sizeof(T) * (size_t)B * N * N));
-    qp_scr_cap = B;
-    HIPCHK(hipMalloc(&dWarm, sizeof(T) * (size_t)N * B));
-    HIPCHK(hipMalloc(&dTmp, sizeof(T) * (size_t)(L * p + n * L + 64)));
-    HIPCHK(hipMemset(dK, 0, sizeof(T) * sK * B));
-    HIPCHK(hipMemset(dC, 0, sizeof(T) * sC * B));
-    HIPCHK(hipMemset(dPsi[0], 0, sizeof(T) * (size_t)L * B));
-    HIPCHK(hipMemset(dPsi[1], 0, sizeof(T) * (size_t)L * B));
-    HIPCHK(hipMemset(dUprev, 0, sizeof(T) * (size_t)B));
-    HIPCHK(hipMemset(dWarm, 0, sizeof(T) * (size_t)N * B));
+    HIPCHK(dP.alloc((size_t)sP * B));
+    HIPCHK(dK.alloc((size_t)sK * B));
+    HIPCHK(dQ.alloc((size_t)sQ * B));
+    HIPCHK(dC.alloc((size_t)sC * B));
+    HIPCHK(dPsi[0].alloc((size_t)L * B));
+    HIPCHK(dPsi[1].alloc((size_t)L * B));
+    HIPCHK(dUprev.alloc((size_t)B));
+    HIPCHK(dQpScr.alloc((size_t)B * N * N));
+    HIPCHK(dWarm.alloc((size_t)N * B));
+    HIPCHK(dTmp.alloc((size_t)(L * p + n * L + 64)));
+    // every block a checkpoint carries starts as zeros, the padding of the strides included (reset() below fills P and bar_Q)
+    const Sections blocks = sections(blob_header());
+    for (int i = 0; i < blocks.n_traj; ++i) HIPCHK(hipMemset(blocks.s[i].ptr, 0, blocks.s[i].bytes()));
+    HIPCHK(hipMemset(dPsi[cur], 0, sizeof(T) * (size_t)L * B));
     if (sizeof(T) == 8 && threads == 256 && !dbg_env("KMPC_QP_NO_CARRY")) {  // (the variable is a measurement aid)
-      HIPCHK(hipMalloc(&dQpCarry, sizeof(T) * (size_t)B * N * N));
-      HIPCHK(hipMalloc(&dQpCarrySet, sizeof(int32_t) * (size_t)B * 4));
+      HIPCHK(dQpCarry.alloc((size_t)B * N * N));
+      HIPCHK(dQpCarrySet.alloc((size_t)B * 4));
       HIPCHK(hipMemset(dQpCarrySet, 0, sizeof(int32_t) * (size_t)B * 4));
     }
     // a dimension set without a built-in fused roll-out gets its kernel now (rollout_plugin.hip: kernel cache, else hipcc, 4-8 s);
@@ -317,7 +348,7 @@ struct Impl : kmpc_handle {
       use_img = fused_dims_ok() && (c.output_kind != KMPC_OUT_LIFT || q == L) && rollout_uses_image(n, L, N, q);
       if (use_img) {
         sImg = state_image_elems(L, n);
-        HIPCHK(hipMalloc(&dImg, sizeof(double) * (size_t)sImg * B));
+        HIPCHK(dImg.alloc((size_t)sImg * B));
       }
     }
     if constexpr (sizeof(T) == 4) {
@@ -343,33 +374,26 @@ struct Impl : kmpc_handle {
       if (Lenc < 1) FAIL(-2, "lift_offset = 2 needs L > n (L = n + the encoder's output dimension)");
       if (enc.hid > 128) FAIL(-2, "hidden + 2 n must not exceed 128 with lift_offset = 2");
       const int Hp = enc.Hp, Lp = enc.Lp;
-      HIPCHK(hipMalloc(&dW1, sizeof(T) * Hp * 4));
-      HIPCHK(hipMalloc(&db1, sizeof(T) * Hp));
+      HIPCHK(dW1.alloc((size_t)Hp * 4));
+      HIPCHK(db1.alloc((size_t)Hp));
       for (int k = 0; k < c.layers - 1; ++k) {
-        HIPCHK(hipMalloc(&dWh[k], sizeof(T) * Hp * Hp));
-        HIPCHK(hipMalloc(&dbh[k], sizeof(T) * Hp));
+        HIPCHK(dWh[k].alloc((size_t)Hp * Hp));
+        HIPCHK(dbh[k].alloc((size_t)Hp));
       }
-      HIPCHK(hipMalloc(&dWo, sizeof(T) * Lp * Hp));
-      HIPCHK(hipMalloc(&dbo, sizeof(T) * Lp));
+      HIPCHK(dWo.alloc((size_t)Lp * Hp));
+      HIPCHK(dbo.alloc((size_t)Lp));
       layer_set.assign(c.layers + 1, false);
       hostW.assign(c.layers + 1, std::vector<double>());
       hostb.assign(c.layers + 1, std::vector<double>());
     } else {
       if (c.lift_offset != 0) FAIL(-2, "lift_offset applies to the MLP encoder only");
-      HIPCHK(hipMalloc(&dcx, sizeof(T) * L * n));
+      HIPCHK(dcx.alloc((size_t)L * n));
     }
     return reset(nullptr);
   }
 
   ~Impl() override {
     delete core;
-    for (void* ptr : {(void*)dP, (void*)dK, (void*)dQ, (void*)dC, (void*)dPsi[0], (void*)dPsi[1], (void*)dUprev, (void*)dWarm,
-                      (void*)dW1, (void*)db1, (void*)dWh[0], (void*)dWh[1], (void*)dbh[0], (void*)dbh[1], (void*)dWo,
-                      (void*)dbo, (void*)dcx, (void*)dTmp, (void*)dU0, (void*)dGram, (void*)dPartial, (void*)dKs, (void*)dCs,
-                      (void*)dHs, (void*)dFs, (void*)df0s, (void*)dWt, (void*)dWhp[0], (void*)dWhp[1], (void*)dWop,
-                      (void*)dDareP, (void*)dDareIt, (void*)dWtB, (void*)dQpScr, (void*)dMsK, (void*)dMsC, (void*)dMsH,
-                      (void*)dMsf, (void*)dMsc, (void*)dMsW, (void*)dTs, (void*)dNeed, (void*)dImg, (void*)dQpCarry, (void*)dQpCarrySet, (void*)dDelta, (void*)dQpList, (void*)dWork, (void*)dPerm, (void*)dTermQ, (void*)dTermScr, (void*)dEyeL, (void*)dFastPack})
-      if (ptr) (void)hipFree(ptr);
     for (auto e : ev) (void)hipEventDestroy(e);
     if (evPlace) (void)hipEventDestroy(evPlace);
   }
@@ -412,15 +436,13 @@ struct Impl : kmpc_handle {
     if constexpr (sizeof(T) == 4) {
       int rc = core->ensure_dense(s, true);
       if (rc) { err = core->err; return rc; }
-      HIPCHK((launch_cast<float, double>((const float*)dP, core->dP, (size_t)sP * B, s)));
-      HIPCHK((launch_cast<float, double>((const float*)dK, core->dK, (size_t)sK * B, s)));
-      HIPCHK((launch_cast<float, double>((const float*)dQ, core->dQ, (size_t)sQ * B, s)));
-      HIPCHK((launch_cast<float, double>((const float*)dC, core->dC, (size_t)sC * B, s)));
-      HIPCHK((launch_cast<float, double>((const float*)dPsi[0], core->dPsi[0], (size_t)L * B, s)));
-      HIPCHK((launch_cast<float, double>((const float*)dPsi[1], core->dPsi[1], (size_t)L * B, s)));
-      HIPCHK((launch_cast<float, double>((const float*)dUprev, core->dUprev, (size_t)B, s)));
-      HIPCHK((launch_cast<float, double>((const float*)dWarm, core->dWarm, (size_t)N * B, s)));
-      core->cur = cur; core->have_prev = have_prev; core->rls_fresh = rls_fresh; core->update_on = update_on;
+      core->cur = cur;  // (both sides' tables name the same psi_{k-1} buffer)
+      const Sections mine = sections(blob_header()), cores = core->sections(core->blob_header());
+      for (int i = 0; i < mine.n_traj; ++i)
+        HIPCHK((launch_cast<float, double>((const float*)mine.s[i].ptr, (double*)cores.s[i].ptr, mine.s[i].count, s)));
+      // (psi_k's buffer is no part of a checkpoint, but it has always travelled with the rest)
+      HIPCHK((launch_cast<float, double>((const float*)dPsi[cur], core->dPsi[cur], (size_t)L * B, s)));
+      core->have_prev = have_prev; core->rls_fresh = rls_fresh; core->update_on = update_on;
       core->cfg.P0 = cfg.P0; core->cfg.barQ0 = cfg.barQ0;
       core->dense_valid = true; core->img_valid = false;
     }
@@ -430,15 +452,12 @@ struct Impl : kmpc_handle {
     if constexpr (sizeof(T) == 4) {
       int rc = core->ensure_dense(s, false);
       if (rc) { err = core->err; return rc; }
-      HIPCHK((launch_cast<double, float>(core->dP, (float*)dP, (size_t)sP * B, s)));
-      HIPCHK((launch_cast<double, float>(core->dK, (float*)dK, (size_t)sK * B, s)));
-      HIPCHK((launch_cast<double, float>(core->dQ, (float*)dQ, (size_t)sQ * B, s)));
-      HIPCHK((launch_cast<double, float>(core->dC, (float*)dC, (size_t)sC * B, s)));
-      HIPCHK((launch_cast<double, float>(core->dPsi[0], (float*)dPsi[0], (size_t)L * B, s)));
-      HIPCHK((launch_cast<double, float>(core->dPsi[1], (float*)dPsi[1], (size_t)L * B, s)));
-      HIPCHK((launch_cast<double, float>(core->dUprev, (float*)dUprev, (size_t)B, s)));
-      HIPCHK((launch_cast<double, float>(core->dWarm, (float*)dWarm, (size_t)N * B, s)));
-      cur = core->cur; have_prev = core->have_prev; rls_fresh = core->rls_fresh;
+      cur = core->cur;
+      const Sections mine = sections(blob_header()), cores = core->sections(core->blob_header());
+      for (int i = 0; i < mine.n_traj; ++i)
+        HIPCHK((launch_cast<double, float>((const double*)cores.s[i].ptr, (float*)mine.s[i].ptr, mine.s[i].count, s)));
+      HIPCHK((launch_cast<double, float>(core->dPsi[cur], (float*)dPsi[cur], (size_t)L * B, s)));
+      have_prev = core->have_prev; rls_fresh = core->rls_fresh;
     }
     return 0;
   }
@@ -603,7 +622,7 @@ struct Impl : kmpc_handle {
     for (int r = 0; r < q; ++r)
       for (int c2 = 0; c2 < q; ++c2) w[(size_t)r * q + c2] = (T)(PN[(size_t)r * q + c2] - (r == c2 ? cfg.Qw : 0.0));
     { const int rc = core_weight(&w); if (rc) return rc; }
-    if (!dWt) HIPCHK(hipMalloc(&dWt, sizeof(T) * (size_t)q * q));
+    HIPCHK(dWt.ensure((size_t)q * q));
     HIPCHK(hipMemcpy(dWt, w.data(), w.size() * sizeof(T), hipMemcpyHostToDevice));
     hostPN.assign(PN, PN + (size_t)q * q);
     have_wterm = true;
@@ -624,9 +643,8 @@ struct Impl : kmpc_handle {
       const int nb = per_traj ? B : 1;
       if (nb == 0) return 0;
       { int rc = ensure_dense(s, false); if (rc) return rc; }
-      DevTmp tQl, tEye;
-      HIPCHK(hipMalloc(&tQl.p, sizeof(double) * (size_t)L * L));
-      double* const dQl = tQl.as<double>();
+      DevBuf<double> dQl;
+      HIPCHK(dQl.alloc((size_t)L * L));
       HIPCHK(hipMemcpyAsync(dQl, Qh, sizeof(double) * (size_t)L * L, hipMemcpyHostToDevice, s));
       { int rc = dare_buffers(nb); if (rc) return rc; }
       { int rc = dare_blocks(nb, dQl, R, maxiter, eps, s); if (rc) return rc; }
@@ -647,21 +665,15 @@ struct Impl : kmpc_handle {
     }
   }
 
-  // Riccati workspace and the terminal block(s) for nb models (kmpc_terminal_from_dare, kmpc_set_terminal_refresh)
+  // Riccati workspace and the terminal block(s) for nb models (kmpc_terminal_from_dare, kmpc_set_terminal_refresh, kmpc_state_import):
+  // all three blocks grow or none does; their contents are not kept
   int dare_buffers(int nb) {
     if (dare_cap >= nb) return 0;
-    double* nP = nullptr; int32_t* nIt = nullptr; double* nW = nullptr;
-    HIPCHK(hipMalloc(&nP, sizeof(double) * (size_t)nb * L * L));
-    HIPCHK(hipMalloc(&nIt, sizeof(int32_t) * (size_t)nb));
-    HIPCHK(hipMalloc(&nW, sizeof(double) * (size_t)nb * q * q));
-    if (dDareP) (void)hipFree(dDareP);
-    if (dDareIt) (void)hipFree(dDareIt);
-    if (dWtB) (void)hipFree(dWtB);
-    dDareP = nP; dDareIt = nIt; dWtB = nW;
+    HIPCHK(replace_together(dDareP, (size_t)nb * L * L, dDareIt, (size_t)nb, dWtB, (size_t)nb * q * q));
     dare_cap = nb;
     return 0;
   }
-  double* dEyeL = nullptr;  // L x L identity: the output map of y = psi
+  DevBuf<double> dEyeL;  // L x L identity: the output map of y = psi
   // P = DARE(A, B, Qdev, R) of the first nb trajectories' current [A B] and their blocks Co P Co' - Qw I -> dWtB   (dare_kernel)
   int dare_blocks(int nb, const double* Qdev, double R, int maxiter, double eps, hipStream_t s) {
     if constexpr (sizeof(T) == 8) {
@@ -670,7 +682,7 @@ struct Impl : kmpc_handle {
       if (lift_out && !dEyeL) {
         std::vector<double> eye((size_t)L * L, 0.0);
         for (int i = 0; i < L; ++i) eye[(size_t)i * L + i] = 1.0;
-        HIPCHK(hipMalloc(&dEyeL, sizeof(double) * (size_t)L * L));
+        HIPCHK(dEyeL.alloc((size_t)L * L));
         HIPCHK(hipMemcpy(dEyeL, eye.data(), sizeof(double) * (size_t)L * L, hipMemcpyHostToDevice));
       }
       DareArgs d{};
@@ -678,7 +690,7 @@ struct Impl : kmpc_handle {
       d.A = (const double*)dK; d.strideA = sK; d.ldA = p;
       d.B = (const double*)dK + L; d.strideB = sK; d.incB = p;
       d.Q = Qdev; d.R = R; d.eps = eps;
-      d.Co = lift_out ? dEyeL : (const double*)dC + (size_t)cfg.out_row0 * L;
+      d.Co = lift_out ? dEyeL.get() : (const double*)dC + (size_t)cfg.out_row0 * L;
       d.strideC = lift_out ? 0 : sC;
       d.P = dDareP; d.K = nullptr; d.PN = dWtB; d.pn_sub_diag = cfg.Qw; d.iters = dDareIt;
       HIPCHK(launch_dare(d, s));
@@ -694,7 +706,7 @@ struct Impl : kmpc_handle {
   int term_every = 0, term_maxiter = 500;
   long term_count = 0;
   double term_R = 0.01, term_eps = 0.01;
-  double *dTermQ = nullptr, *dTermScr = nullptr;
+  DevBuf<double> dTermQ, dTermScr;
   int set_terminal_refresh(int every, const double* Qh, double R, int maxiter, double eps) override {
     if constexpr (sizeof(T) != 8) {
       FAIL(-2, "kmpc_set_terminal_refresh: float64 handles only (the reference's Riccati iteration is float64)");
@@ -719,14 +731,14 @@ struct Impl : kmpc_handle {
         for (int b = 0; b < B; ++b) std::copy(w0.begin(), w0.end(), wb.begin() + (size_t)b * q * q);
         HIPCHK(hipMemcpy(dWtB, wb.data(), sizeof(double) * wb.size(), hipMemcpyHostToDevice));
       }
-      if (!dTermQ) HIPCHK(hipMalloc(&dTermQ, sizeof(double) * (size_t)L * L));
+      HIPCHK(dTermQ.ensure((size_t)L * L));
       HIPCHK(hipMemcpy(dTermQ, Qh, sizeof(double) * (size_t)L * L, hipMemcpyHostToDevice));
       have_wterm = true; wterm_from_dare = true; wterm_per_traj = true;
       term_R = R; term_maxiter = maxiter; term_eps = eps; term_count = 0;
       // the fused roll-out of this configuration with the refresh inside: a plug-in of its own (also for the built-in dimension sets)
       variant[1][0].state = 0;
       if (fused_dims_ok()) load_variant(true, false);
-      if (variant[1][0].state > 0 && !dTermScr) HIPCHK(hipMalloc(&dTermScr, sizeof(double) * (size_t)B * term_scratch_elems(L)));
+      if (variant[1][0].state > 0) HIPCHK(dTermScr.ensure((size_t)B * term_scratch_elems(L)));
       term_every = every;
       if (diag_on) (void)load_diag_plugins();  // (diagnostics armed before the refresh: the variant that has both)
       return 0;
@@ -852,10 +864,8 @@ struct Impl : kmpc_handle {
           for (int k = 0; k < L; ++k) acc += barX0[(size_t)r * L + k] * barQ0m[(size_t)k * L + c2];
           hC[(size_t)r * L + c2] = (T)acc;
         }
-    DevTmp ttmp;
-    const size_t tot = hP.size() + hQ.size() + hK.size() + hC.size();
-    HIPCHK(hipMalloc(&ttmp.p, sizeof(T) * tot));
-    T* const tmp = ttmp.as<T>();
+    DevBuf<T> tmp;
+    HIPCHK(tmp.alloc(hP.size() + hQ.size() + hK.size() + hC.size()));
     T* tP = tmp; T* tQ = tP + hP.size(); T* tK = tQ + hQ.size(); T* tC = tK + hK.size();
     HIPCHK(hipMemcpyAsync(tP, hP.data(), sizeof(T) * hP.size(), hipMemcpyHostToDevice, s));
     HIPCHK(hipMemcpyAsync(tQ, hQ.data(), sizeof(T) * hQ.size(), hipMemcpyHostToDevice, s));
@@ -913,7 +923,7 @@ struct Impl : kmpc_handle {
     a.out_kind = cfg.output_kind == KMPC_OUT_LIFT ? OUT_LIFT : OUT_CX;
     a.max_iter = cfg.qp_max_iter > 0 ? cfg.qp_max_iter : 8 * N + 40;
     a.P = dP; a.strideP = sP; a.K = dK; a.strideK = sK; a.Qb = dQ; a.strideQ = sQ; a.C = dC; a.strideC = sC;
-    a.Wterm = have_wterm ? (wterm_from_dare ? (T*)dWtB : dWt) : nullptr;
+    a.Wterm = have_wterm ? (wterm_from_dare ? (T*)dWtB.get() : dWt.get()) : nullptr;
     a.wterm_per_traj = (have_wterm && wterm_from_dare && wterm_per_traj) ? 1 : 0;
     a.lam = (T)cfg.lambda; a.Qw = (T)cfg.Qw; a.Rw = (T)cfg.Rw; a.lb = (T)cfg.lb; a.ub = (T)cfg.ub;
     a.du_mode = cfg.delta_u ? 1 : 0;
@@ -964,7 +974,7 @@ struct Impl : kmpc_handle {
   }
 
   // kmpc_mpc_solve: the solve wrapper with the model as an argument; scratch model blocks, H, f, c are the handle's
-  T *dMsK = nullptr, *dMsC = nullptr, *dMsH = nullptr, *dMsf = nullptr, *dMsc = nullptr, *dMsW = nullptr;
+  DevBuf<T> dMsK, dMsC, dMsH, dMsf, dMsc, dMsW;
   int mpc_solve(const void* A, const void* Bv, const void* C, int shared, const void* psi, const void* ref, int rpt,
                 double lb_, double ub_, double Qw_, double Rw_, const double* PN, void* U, void* U0, void* fun,
                 int32_t* st, int32_t* it, int Bc, hipStream_t s) override {
@@ -973,14 +983,12 @@ struct Impl : kmpc_handle {
     if (cfg.output_kind == KMPC_OUT_CX && !C) FAIL(-3, "kmpc_mpc_solve: C is required for KMPC_OUT_CX");
     if (cfg.delta_u) FAIL(-3, "kmpc_mpc_solve: not available in the delta-u form (its state includes the handle's u_prev)");
     if (!(ub_ > lb_)) FAIL(-3, "kmpc_mpc_solve: need lb < ub");
-    if (!dMsK) {
-      HIPCHK(hipMalloc(&dMsK, sizeof(T) * (size_t)sK * B));
-      HIPCHK(hipMalloc(&dMsC, sizeof(T) * (size_t)sC * B));
-      HIPCHK(hipMalloc(&dMsH, sizeof(T) * (size_t)B * N * N));
-      HIPCHK(hipMalloc(&dMsf, sizeof(T) * (size_t)B * N));
-      HIPCHK(hipMalloc(&dMsc, sizeof(T) * (size_t)B));
-      HIPCHK(hipMalloc(&dMsW, sizeof(T) * (size_t)q * q));
-    }
+    HIPCHK(dMsK.ensure((size_t)sK * B));  // (each on its own: a call that failed half-way leaves nothing the next one trips over)
+    HIPCHK(dMsC.ensure((size_t)sC * B));
+    HIPCHK(dMsH.ensure((size_t)B * N * N));
+    HIPCHK(dMsf.ensure((size_t)B * N));
+    HIPCHK(dMsc.ensure((size_t)B));
+    HIPCHK(dMsW.ensure((size_t)q * q));
     HIPCHK(launch_import_model<T>((const T*)A, (const T*)Bv, (const T*)C, shared, n, L, B, dMsK, sK,
                                   cfg.output_kind == KMPC_OUT_CX ? dMsC : nullptr, sC, s));
     if (PN) {
@@ -1021,16 +1029,14 @@ struct Impl : kmpc_handle {
     if (n != 2) FAIL(-3, "plants are two-state systems");
     if (!plant_id_ok(plant)) FAIL(-3, "unknown plant");
     const size_t M = (size_t)n_traj * n_steps;
-    T *gx = nullptr, *gy = nullptr;
-    if (!Xo) HIPCHK(hipMalloc(&gx, sizeof(T) * 2 * M));
-    if (!Yo) { hipError_t e = hipMalloc(&gy, sizeof(T) * 2 * M); if (e != hipSuccess) { if (gx) (void)hipFree(gx); HIPCHK(e); } }
-    T* Xp = Xo ? (T*)Xo : gx; T* Yp = Yo ? (T*)Yo : gy;
+    DevBuf<T> gx, gy;  // the panels the caller did not ask for
+    if (!Xo) HIPCHK(gx.alloc(2 * M));
+    if (!Yo) HIPCHK(gy.alloc(2 * M));
+    T* Xp = Xo ? (T*)Xo : gx.get(); T* Yp = Yo ? (T*)Yo : gy.get();
     int rc = 0;
     hipError_t e = launch_datagen<T>(plant, (T)hs, (const T*)X0, (const T*)U, n_traj, n_steps, Xp, Yp, s);
     if (e != hipSuccess) { err = std::string("kmpc_generate_and_fit: ") + hipGetErrorString(e); rc = -(int)(1000 + (int)e); }
     if (!rc) rc = offline_fit(Xp, Yp, U, (int)M, ridge, init_rls, A, Bm, C, s);  // (synchronises the stream before it returns)
-    if (gx) (void)hipFree(gx);
-    if (gy) (void)hipFree(gy);
     return rc;
   }
 
@@ -1038,12 +1044,9 @@ struct Impl : kmpc_handle {
     if (Bc == 0) return 0;  // empty batch: nothing to do
     if (Bc < 0 || !H || !f || !U) FAIL(-3, "kmpc_qp_solve: bad arguments");
     if (cfg.delta_u && Bc != B) FAIL(-3, "kmpc_qp_solve: with delta_u the batch must equal the handle's (per-trajectory u_prev)");
-    if (Bc > qp_scr_cap) {  // (a stateless solve may bring a larger batch than the handle's)
+    if ((size_t)Bc * N * N > dQpScr.capacity()) {  // (a stateless solve may bring a larger batch than the handle's)
       HIPCHK(hipStreamSynchronize(s));
-      (void)hipFree(dQpScr);
-      dQpScr = nullptr; qp_scr_cap = 0;
-      HIPCHK(hipMalloc(&dQpScr, sizeof(T) * (size_t)Bc * N * N));
-      qp_scr_cap = Bc;
+      HIPCHK(dQpScr.grow((size_t)Bc * N * N));
     }
     StepArgs<T> a = base_args(Bc);
     a.phases = PH_QP;
@@ -1120,7 +1123,7 @@ struct Impl : kmpc_handle {
       }
       if (term_count % term_every == 0) { const int rc2 = dare_blocks(B, dTermQ, term_R, term_maxiter, term_eps, s); if (rc2) return rc2; }
       a.phases = ph & ~PH_RLS;
-      a.Wterm = (T*)dWtB; a.wterm_per_traj = 1;
+      a.Wterm = (T*)dWtB.get(); a.wterm_per_traj = 1;
       term_count += 1;
     }
     HIPCHK(launch_step<T>(a, threads, s));
@@ -1154,7 +1157,7 @@ struct Impl : kmpc_handle {
   }
 
   // ---- fused roll-out (one launch for all the steps; rollout_kernel in step_kernel.hip) ----------------
-  T *dWhp[2] = {nullptr, nullptr}, *dWop = nullptr;  // hidden / output weights as MFMA A-fragments
+  DevBuf<T> dWhp[2], dWop;  // hidden / output weights as MFMA A-fragments
   bool packed_ok = false;
   int64_t prof_steps = 0;   // profiling: control steps covered by the recorded events
   int pack_encoder(hipStream_t s) {
@@ -1162,10 +1165,10 @@ struct Impl : kmpc_handle {
     const int KS = enc.KS;
     const int nhh = cfg.layers - 1;
     for (int k = 0; k < nhh; ++k) {
-      if (!dWhp[k]) HIPCHK(hipMalloc(&dWhp[k], sizeof(T) * (size_t)(enc.Hp / 16) * KS * 64));
+      HIPCHK(dWhp[k].ensure((size_t)(enc.Hp / 16) * KS * 64));
       HIPCHK(launch_pack_afrag<T>(dWh[k], enc.Hp, enc.Hp, KS, dWhp[k], s));
     }
-    if (!dWop) HIPCHK(hipMalloc(&dWop, sizeof(T) * (size_t)(enc.Lp / 16) * KS * 64));
+    HIPCHK(dWop.ensure((size_t)(enc.Lp / 16) * KS * 64));
     HIPCHK(launch_pack_afrag<T>(dWo, enc.Lp, enc.Hp, KS, dWop, s));
     packed_ok = true;
     return 0;
@@ -1257,7 +1260,7 @@ struct Impl : kmpc_handle {
     const bool global_place = cfg.lift_kind == KMPC_LIFT_MLP && (B & 15) == 0 && B <= (1 << 20);
     if (!dbg_env("KMPC_ROLLOUT_NO_PLACE")) {  // (the trajectories' solver work of the previous launch: RolloutArgs::work)
       if (!dWork) {
-        HIPCHK(hipMalloc(&dWork, sizeof(int32_t) * (size_t)B));
+        HIPCHK(dWork.alloc((size_t)B));
         HIPCHK(hipMemsetAsync(dWork, 0, sizeof(int32_t) * (size_t)B, s));
       }
       r.work = dWork;
@@ -1281,7 +1284,7 @@ struct Impl : kmpc_handle {
     //  9 us at B = 4096 were counted into "the dominant kernel's duration": rocprofv3 0.630 ms against 0.647 ms from these events)
     if (rec && (rc = prof_end(s, steps))) return rc;
     if (r.work && steps >= 4 && global_place) {
-      if (!dPerm) HIPCHK(hipMalloc(&dPerm, sizeof(int32_t) * (size_t)B * 3));  // (perm, then the sort's two ping-pong buffers)
+      HIPCHK(dPerm.ensure((size_t)B * 3));  // (perm, then the sort's two ping-pong buffers)
       HIPCHK(launch_place(dWork, B, dPerm, reinterpret_cast<uint32_t*>(dPerm + B), s));  // (the next launch's deal: RolloutArgs::perm)
       place_valid = true;
     } else {
@@ -1300,7 +1303,7 @@ struct Impl : kmpc_handle {
     return 0;
   }
 
-  T* dU0 = nullptr;  // rollout scratch [B]
+  DevBuf<T> dU0;  // rollout scratch [B]
   int rollout(int plant, void* X, const void* ref, int rpt, int steps, int step0, int switch_step, double hs,
               void* Ulog, void* Xlog, int32_t* st, int32_t* it, hipStream_t s) override {
     return rollout_impl(StepCtx{}, plant, X, ref, rpt, steps, step0, switch_step, hs, Ulog, Xlog, st, it, s);
@@ -1308,7 +1311,7 @@ struct Impl : kmpc_handle {
   int rollout_impl(const StepCtx& ctx, int plant, void* X, const void* ref, int rpt, int steps, int step0, int switch_step, double hs,
                    void* Ulog, void* Xlog, int32_t* st, int32_t* it, hipStream_t s) {
     if (!X || !ref || steps < 0) FAIL(-3, "kmpc_rollout: bad arguments");
-    if (!dU0) HIPCHK(hipMalloc(&dU0, sizeof(T) * (size_t)B));
+    HIPCHK(dU0.ensure((size_t)B));
     if (n != 2) FAIL(-3, "plants are two-state systems");
     if (!plant_id_ok(plant)) FAIL(-3, "unknown plant");
     // (the fused roll-out with the MLP lift accumulates status / iterations in LDS and WRITES them when it ends: no zeroing
@@ -1354,44 +1357,51 @@ struct Impl : kmpc_handle {
   }
 
   // ---- shared-model mode -----------------------------------------------------------------------------
-  double *dGram = nullptr, *dPartial = nullptr;
-  T *dKs = nullptr, *dCs = nullptr, *dHs = nullptr, *dFs = nullptr, *df0s = nullptr, *dTs = nullptr;
-  double* dFastPack = nullptr;   // F, T0, H of the shared model as shared_fast_kernel's operand fragments (SharedModel2Args::pack)
+  DevBuf<double> dGram, dPartial;  // (dGram set: the handle has its shared-model blocks, all seven -- shared_alloc)
+  DevBuf<T> dKs, dCs, dHs, dFs, df0s, dTs;
+  DevBuf<double> dFastPack;      // F, T0, H of the shared model as shared_fast_kernel's operand fragments (SharedModel2Args::pack)
   bool fast_pack_valid = false;  // ... written by the last model launch
-  int32_t* dNeed = nullptr;  // [B] flags of shared_fast_kernel
-  int32_t* dWork = nullptr;  // [B] solver work of every trajectory in the last fused launch (RolloutArgs::work)
-  int32_t* dPerm = nullptr;  // [B] slot -> trajectory for the next fused launch (RolloutArgs::perm); valid after a launch that wrote dWork
+  DevBuf<int32_t> dNeed;  // [B] flags of shared_fast_kernel
+  DevBuf<int32_t> dWork;  // [B] solver work of every trajectory in the last fused launch (RolloutArgs::work)
+  DevBuf<int32_t> dPerm;  // [B] slot -> trajectory for the next fused launch (RolloutArgs::perm); valid after a launch that wrote dWork
   bool place_valid = false;
   hipEvent_t evPlace = nullptr;      // recorded behind the launch (and the rank pass) that wrote dWork / dPerm
   hipStream_t place_stream = nullptr;
-  int32_t* dQpList = nullptr;  // two alternating counters, then the list of the trajectories shared_fast_kernel left to the solve-only kernel
+  DevBuf<int32_t> dQpList;  // two alternating counters, then the list of the trajectories shared_fast_kernel left to the solve-only kernel
   int qp_list_parity = 0;
-  T* dWt = nullptr;  // PN - Qw I (terminal block of Q_bar)
+  DevBuf<T> dWt;  // PN - Qw I (terminal block of Q_bar)
   std::vector<double> hostPN;  // P_N as given to kmpc_set_terminal_weight
   bool have_wterm = false;
   // kmpc_terminal_from_dare: Riccati workspace and the block(s) it produced ([1] or [B][q*q], PN - Qw I)
-  double* dDareP = nullptr; int32_t* dDareIt = nullptr; double* dWtB = nullptr;
-  int dare_cap = 0;
+  DevBuf<double> dDareP, dWtB;
+  DevBuf<int32_t> dDareIt;
+  int dare_cap = 0;  // models the three hold room for (dare_buffers alone changes it)
   bool wterm_from_dare = false, wterm_per_traj = false;
   bool shared_has_samples = false;
   static constexpr int GRAM_BLOCKS = 256;  // partial blocks of the Gram kernels (512 measured slower: lift + Gram 21.8 vs 17.2 us, reduce 7.6 vs 4.8 us)
   int64_t gram_elems() const override { return (int64_t)(p + L + n) * p; }
+  // the seven blocks of the shared-model mode, made and filled in locals and handed to the handle together: a call that fails leaves the
+  // handle without any of them, and the next one starts over
   int shared_alloc() {
     if (dGram) return 0;
     const int R = p + L + n, MT = (R + 15) / 16, NT = (p + 15) / 16;
-    HIPCHK(hipMalloc(&dGram, sizeof(double) * (size_t)R * p));
-    HIPCHK(hipMemset(dGram, 0, sizeof(double) * (size_t)R * p));
-    HIPCHK(hipMalloc(&dPartial, sizeof(double) * (size_t)GRAM_BLOCKS * MT * 16 * NT * 16));
-    HIPCHK(hipMalloc(&dKs, sizeof(T) * (size_t)L * p));
-    HIPCHK(hipMalloc(&dCs, sizeof(T) * (size_t)n * L));
-    HIPCHK(hipMalloc(&dHs, sizeof(T) * (size_t)N * N));
-    HIPCHK(hipMalloc(&dFs, sizeof(T) * (size_t)N * (L + 1)));  // (one more column in the delta-u form)
-    HIPCHK(hipMalloc(&df0s, sizeof(T) * (size_t)N));
+    DevBuf<double> gram, partial;
+    DevBuf<T> ks, cs, hs, fs, f0s;
+    HIPCHK(gram.alloc((size_t)R * p));
+    HIPCHK(hipMemset(gram, 0, sizeof(double) * (size_t)R * p));
+    HIPCHK(partial.alloc((size_t)GRAM_BLOCKS * MT * 16 * NT * 16));
+    HIPCHK(ks.alloc((size_t)L * p));
+    HIPCHK(cs.alloc((size_t)n * L));
+    HIPCHK(hs.alloc((size_t)N * N));
+    HIPCHK(fs.alloc((size_t)N * (L + 1)));  // (one more column in the delta-u form)
+    HIPCHK(f0s.alloc((size_t)N));
     // until samples exist the shared model is the offline one (trajectory 0's copy, duffing.py:811-813)
     { int rc = sync_own(); if (rc) return rc; }  // (before the conversion: non-blocking streams do not order with the null stream)
     { int rc = ensure_dense(nullptr, false); if (rc) return rc; HIPCHK(hipStreamSynchronize(nullptr)); }
-    HIPCHK(hipMemcpy(dKs, dK, sizeof(T) * (size_t)L * p, hipMemcpyDeviceToDevice));
-    HIPCHK(hipMemcpy(dCs, dC, sizeof(T) * (size_t)n * L, hipMemcpyDeviceToDevice));
+    HIPCHK(hipMemcpy(ks, dK, sizeof(T) * (size_t)L * p, hipMemcpyDeviceToDevice));
+    HIPCHK(hipMemcpy(cs, dC, sizeof(T) * (size_t)n * L, hipMemcpyDeviceToDevice));
+    dGram = std::move(gram); dPartial = std::move(partial);
+    dKs = std::move(ks); dCs = std::move(cs); dHs = std::move(hs); dFs = std::move(fs); df0s = std::move(f0s);
     return 0;
   }
   int shared_local_gram(const void* X, double* delta, hipStream_t s) override {
@@ -1443,7 +1453,7 @@ struct Impl : kmpc_handle {
     return shared_solve_impl(StepCtx{false, plant, switched ? 1 : 0, hstep, X, nullptr}, delta, ref, U0, Useq, st, it, s);
   }
   // kmpc_shared_rollout: the stages of the shared-model step, `steps` times, on one stream, the collective between them
-  double* dDelta = nullptr;  // this rank's Gram sums of a step (all-reduced in place)
+  DevBuf<double> dDelta;  // this rank's Gram sums of a step (all-reduced in place)
   int shared_rollout(int plant, void* X, const void* ref, int steps, int step0, int switch_step, double hstep, void* comm, void* Ulog,
                      void* Xlog, void* U0out, void* Useq, int32_t* st, int32_t* it, hipStream_t s) override {
     if (!X || !ref || steps < 0) FAIL(-3, "kmpc_shared_rollout: bad arguments");
@@ -1451,8 +1461,8 @@ struct Impl : kmpc_handle {
     if (!plant_id_ok(plant)) FAIL(-3, "unknown plant");
     int rc = shared_alloc();
     if (rc) return rc;
-    if (!dDelta) HIPCHK(hipMalloc(&dDelta, sizeof(double) * (size_t)gram_elems()));
-    if (!dU0) HIPCHK(hipMalloc(&dU0, sizeof(T) * (size_t)B));
+    HIPCHK(dDelta.ensure((size_t)gram_elems()));
+    HIPCHK(dU0.ensure((size_t)B));
     typedef ncclResult_t (*allreduce_fn)(const void*, void*, size_t, ncclDataType_t, ncclRedOp_t, ncclComm_t, hipStream_t);
     allreduce_fn ar = nullptr;
     if (comm) {
@@ -1487,7 +1497,7 @@ struct Impl : kmpc_handle {
     int rc = shared_alloc();
     if (rc) return rc;
     if (core && (rc = ensure_dense(s, true))) return rc;
-    const T* wt = !have_wterm ? nullptr : (wterm_from_dare ? (const T*)dWtB : dWt);
+    const T* wt = !have_wterm ? nullptr : (wterm_from_dare ? (const T*)dWtB.get() : dWt.get());
     const int okind = cfg.output_kind == KMPC_OUT_LIFT ? OUT_LIFT : OUT_CX;
     const int cy0 = cfg.output_kind == KMPC_OUT_LIFT ? 0 : cfg.out_row0;
     static const bool two_kernels = dbg_env("KMPC_SHARED_TWO_KERNELS") != nullptr;  // measurement aid: the round-1 launches
@@ -1495,7 +1505,7 @@ struct Impl : kmpc_handle {
     if (have_prev && !one_launch) HIPCHK(launch_axpby(dGram, delta, cfg.lambda, (int)gram_elems(), s));
     if (one_launch) {
       // model solve + condensed QP + the tableau the box QPs start from, one launch (shared_model_kernel)
-      if (!dTs) HIPCHK(hipMalloc(&dTs, sizeof(T) * (size_t)N * N));
+      HIPCHK(dTs.ensure((size_t)N * N));
       const bool old_kernel = dbg_env("KMPC_SHARED_MODEL_R3") != nullptr;  // measurement / test aid (read per call): the round-3 model kernel
       bool on16 = false;
       if constexpr (sizeof(T) == 8) {
@@ -1510,9 +1520,9 @@ struct Impl : kmpc_handle {
           int fmt = 0, fk1 = 0, fk2 = 0;
           if (N <= 64 && shared_fast_shape(N, L + (cfg.delta_u ? 1 : 0), &fmt, &fk1, &fk2)) {
             if (!dFastPack) {
-              const size_t bytes = sizeof(double) * shared_fast_pack_elems(fmt, fk1, fk2);
-              HIPCHK(hipMalloc(&dFastPack, bytes));
-              HIPCHK(hipMemsetAsync(dFastPack, 0, bytes, s));  // (the padding of the fragments stays zero: only elements of the matrices are written)
+              const size_t elems = shared_fast_pack_elems(fmt, fk1, fk2);
+              HIPCHK(dFastPack.alloc(elems));
+              HIPCHK(hipMemsetAsync(dFastPack, 0, sizeof(double) * elems, s));  // (the padding of the fragments stays zero: only elements of the matrices are written)
             }
             m.pack = dFastPack; m.pack_mt = fmt; m.pack_ks1 = fk1; m.pack_ks2 = fk2;
           }
@@ -1553,10 +1563,10 @@ struct Impl : kmpc_handle {
     // (shared_fast_kernel); the solve-only kernel then only runs for the flagged rest
     const bool no_fast = dbg_env("KMPC_SHARED_NO_FAST") != nullptr;  // measurement / test aid (read per call): every trajectory through the QP kernel
     if (one_launch && sizeof(T) == 8 && N <= 64 && !no_fast) {
-      if (!dNeed) HIPCHK(hipMalloc(&dNeed, sizeof(int32_t) * (size_t)B));
+      HIPCHK(dNeed.ensure((size_t)B));
       // (the flagged trajectories also go into a list that a fixed grid of the solve-only kernel walks; two counters alternate)
       if (!dQpList) {
-        HIPCHK(hipMalloc(&dQpList, sizeof(int32_t) * (size_t)(B + 2)));
+        HIPCHK(dQpList.alloc((size_t)(B + 2)));
         HIPCHK(hipMemsetAsync(dQpList, 0, sizeof(int32_t) * (size_t)(B + 2), s));
       }
       if (!dbg_env("KMPC_SHARED_NO_LIST")) {  // (measurement / test aid, read per call: one workgroup per trajectory, flags only)
@@ -1581,13 +1591,12 @@ struct Impl : kmpc_handle {
     if (rc) return rc;
     if ((rc = ensure_dense(s, true))) return rc;
     if ((rc = forget_tableaux(s))) return rc;
-    DevTmp tpx, tpy, tpinv, tg;
-    if (init_rls) HIPCHK(hipMalloc(&tpinv.p, sizeof(T) * (size_t)(p * p + L * L)));
-    HIPCHK(hipMalloc(&tpx.p, sizeof(T) * (size_t)L * M));
-    HIPCHK(hipMalloc(&tpy.p, sizeof(T) * (size_t)L * M));
-    HIPCHK(hipMalloc(&tg.p, sizeof(double) * (size_t)gram_elems()));
-    T* const px = tpx.as<T>(); T* const py = tpy.as<T>(); T* const pinv = tpinv.as<T>();
-    double* const g = tg.as<double>();
+    DevBuf<T> px, py, pinv;  // (pinv stays empty without init_rls)
+    DevBuf<double> g;
+    if (init_rls) HIPCHK(pinv.alloc((size_t)(p * p + L * L)));
+    HIPCHK(px.alloc((size_t)L * M));
+    HIPCHK(py.alloc((size_t)L * M));
+    HIPCHK(g.alloc((size_t)gram_elems()));
     rc = lift_to((const T*)X, px, M, 1, M, s);           // panels (L x M)
     if (!rc) rc = lift_to((const T*)Y, py, M, 1, M, s);
     if (!rc) {
@@ -1628,21 +1637,34 @@ struct Impl : kmpc_handle {
     return 0;
   }
 
-  // ---- state blob (version 2): header | P | K | Q | C | psi_prev | last minimiser | u_prev
-  //      | shared-model section (Gram sums, shared [A B], C) when the handle has one
-  //      | terminal-weight section (PN - Qw I: one block, or the Riccati blocks of kmpc_terminal_from_dare)
-  struct BlobHeader {
-    int32_t magic, version, dtype, n, L, N, B, have_prev, rls_fresh;
-    int32_t has_shared, shared_has_samples, have_wterm, wterm_from_dare, wterm_per_traj, wterm_blocks, reserved;
-    double P0, barQ0;
-  };
-  int64_t base_elems() const { return (sP + sK + sQ + sC) * (int64_t)B + (int64_t)L * B + B + (int64_t)N * B; }
-  int64_t shared_bytes() const { return dGram ? (int64_t)sizeof(double) * gram_elems() + (int64_t)sizeof(T) * ((int64_t)L * p + (int64_t)n * L) : 0; }
-  int64_t wterm_blocks() const { return !have_wterm ? 0 : (wterm_from_dare ? (wterm_per_traj ? B : 1) : 1); }
-  int64_t wterm_bytes() const { return !have_wterm ? 0 : (wterm_from_dare ? (int64_t)sizeof(double) : (int64_t)sizeof(T)) * wterm_blocks() * q * q; }
-  int64_t state_bytes() const override {
-    return (int64_t)sizeof(BlobHeader) + (int64_t)sizeof(T) * base_elems() + shared_bytes() + wterm_bytes();
+  // ---- state blob (the layout: the comment at BlobHeader, above Impl)
+  int32_t wterm_block_count(bool have, bool from_dare, bool per_traj) const { return !have ? 0 : ((from_dare && per_traj) ? B : 1); }
+  // the header of a blob written now: which optional sections the handle has, and the flags that travel with the state
+  BlobHeader blob_header() const {
+    BlobHeader hd{};
+    hd.magic = kBlobMagic; hd.version = 2; hd.dtype = cfg.dtype; hd.n = n; hd.L = L; hd.N = N; hd.B = B;
+    hd.have_prev = have_prev ? 1 : 0; hd.rls_fresh = rls_fresh ? 1 : 0;
+    hd.has_shared = dGram ? 1 : 0; hd.shared_has_samples = shared_has_samples ? 1 : 0;
+    hd.have_wterm = have_wterm ? 1 : 0; hd.wterm_from_dare = wterm_from_dare ? 1 : 0; hd.wterm_per_traj = wterm_per_traj ? 1 : 0;
+    hd.wterm_blocks = wterm_block_count(have_wterm, wterm_from_dare, wterm_per_traj);
+    hd.P0 = cfg.P0; hd.barQ0 = cfg.barQ0;
+    return hd;
   }
+  // THE list of the state blocks: what a blob with header hd holds behind it, in its order, as this handle's buffers.  Checkpoints
+  // (size, export, import), the float32 <-> float64 hand-over (core_push / core_pull: the first n_traj entries) and the zero-fill of
+  // init all walk this list.  (Pointers of sections the handle has not allocated are null: sizes are valid before, copies after.)
+  Sections sections(const BlobHeader& hd) const {
+    Sections t;
+    t.add(dP, sizeof(T), (size_t)sP * B); t.add(dK, sizeof(T), (size_t)sK * B);
+    t.add(dQ, sizeof(T), (size_t)sQ * B); t.add(dC, sizeof(T), (size_t)sC * B);
+    t.add(dPsi[cur ^ 1], sizeof(T), (size_t)L * B); t.add(dWarm, sizeof(T), (size_t)N * B); t.add(dUprev, sizeof(T), (size_t)B);
+    t.n_traj = t.n;
+    if (hd.has_shared) { t.add(dGram, sizeof(double), (size_t)gram_elems()); t.add(dKs, sizeof(T), (size_t)L * p); t.add(dCs, sizeof(T), (size_t)n * L); }
+    if (hd.have_wterm && hd.wterm_from_dare) t.add(dWtB, sizeof(double), (size_t)hd.wterm_blocks * q * q);
+    else if (hd.have_wterm) t.add(dWt, sizeof(T), (size_t)hd.wterm_blocks * q * q);
+    return t;
+  }
+  int64_t state_bytes() const override { return sections(blob_header()).blob_bytes(); }
   int state_export(void* blob, int64_t bytes) override {
     if (bytes < state_bytes() || !blob) FAIL(-3, "kmpc_state_export: buffer too small");
     { int rc = sync_own(); if (rc) return rc; }  // (a roll-out on a non-blocking stream may still be writing the wave image)
@@ -1650,26 +1672,13 @@ struct Impl : kmpc_handle {
     { int rc = forget_tableaux(nullptr); if (rc) return rc; }  // (a checkpoint is a synchronisation point: exporter and importer continue alike)
     if (core) img_valid = false;  // (... a float32 handle from its float32 blocks, as the importer will, not from its core's unrounded state)
     HIPCHK(hipStreamSynchronize(nullptr));
-    BlobHeader hd{};
-    hd.magic = 0x4b4d5043; hd.version = 2; hd.dtype = cfg.dtype; hd.n = n; hd.L = L; hd.N = N; hd.B = B;
-    hd.have_prev = have_prev ? 1 : 0; hd.rls_fresh = rls_fresh ? 1 : 0;
-    hd.has_shared = dGram ? 1 : 0; hd.shared_has_samples = shared_has_samples ? 1 : 0;
-    hd.have_wterm = have_wterm ? 1 : 0; hd.wterm_from_dare = wterm_from_dare ? 1 : 0; hd.wterm_per_traj = wterm_per_traj ? 1 : 0;
-    hd.wterm_blocks = (int32_t)wterm_blocks();
-    hd.P0 = cfg.P0; hd.barQ0 = cfg.barQ0;
+    const BlobHeader hd = blob_header();
+    const Sections t = sections(hd);
     char* o = (char*)blob;  // host or device memory (unified addressing)
     HIPCHK(hipMemcpy(o, &hd, sizeof(hd), hipMemcpyDefault)); o += sizeof(hd);
-    struct { const void* ptr; size_t bytes; } parts[] = {
-        {dP, sizeof(T) * (size_t)sP * B}, {dK, sizeof(T) * (size_t)sK * B}, {dQ, sizeof(T) * (size_t)sQ * B},
-        {dC, sizeof(T) * (size_t)sC * B}, {dPsi[cur ^ 1], sizeof(T) * (size_t)L * B}, {dWarm, sizeof(T) * (size_t)N * B},
-        {dUprev, sizeof(T) * (size_t)B},
-        {dGram, dGram ? sizeof(double) * (size_t)gram_elems() : 0}, {dKs, dGram ? sizeof(T) * (size_t)L * p : 0},
-        {dCs, dGram ? sizeof(T) * (size_t)n * L : 0},
-        {have_wterm ? (wterm_from_dare ? (const void*)dWtB : (const void*)dWt) : nullptr, (size_t)wterm_bytes()}};
-    for (auto& pt : parts) {
-      if (!pt.bytes) continue;
-      HIPCHK(hipMemcpy(o, pt.ptr, pt.bytes, hipMemcpyDefault));
-      o += pt.bytes;
+    for (int i = 0; i < t.n; ++i) {
+      HIPCHK(hipMemcpy(o, t.s[i].ptr, t.s[i].bytes(), hipMemcpyDefault));
+      o += t.s[i].bytes();
     }
     return 0;
   }
@@ -1678,7 +1687,7 @@ struct Impl : kmpc_handle {
     BlobHeader hd;
     const char* o = (const char*)blob;
     HIPCHK(hipMemcpy(&hd, o, sizeof(hd), hipMemcpyDefault)); o += sizeof(hd);
-    if (hd.magic != 0x4b4d5043 || hd.version != 2 || hd.dtype != cfg.dtype || hd.n != n || hd.L != L || hd.N != N || hd.B != B)
+    if (hd.magic != kBlobMagic || hd.version != 2 || hd.dtype != cfg.dtype || hd.n != n || hd.L != L || hd.N != N || hd.B != B)
       FAIL(-3, "kmpc_state_import: blob does not match this handle");
     // a consistent header: flags are 0 / 1, the number of terminal blocks is what the flags imply, Riccati blocks only where
     // kmpc_terminal_from_dare would have produced them (float64)  (round-1 blobs, version 1, are not accepted: they carry no
@@ -1687,44 +1696,23 @@ struct Impl : kmpc_handle {
     if (!flag01(hd.have_prev) || !flag01(hd.rls_fresh) || !flag01(hd.has_shared) || !flag01(hd.shared_has_samples) || !flag01(hd.have_wterm) ||
         !flag01(hd.wterm_from_dare) || !flag01(hd.wterm_per_traj))
       FAIL(-3, "kmpc_state_import: inconsistent header (flags)");
-    const int32_t want_blocks = !hd.have_wterm ? 0 : ((hd.wterm_from_dare && hd.wterm_per_traj) ? B : 1);
-    if (hd.wterm_blocks != want_blocks || (!hd.have_wterm && (hd.wterm_from_dare || hd.wterm_per_traj)) || (hd.wterm_per_traj && !hd.wterm_from_dare))
+    if (hd.wterm_blocks != wterm_block_count(hd.have_wterm, hd.wterm_from_dare, hd.wterm_per_traj) ||
+        (!hd.have_wterm && (hd.wterm_from_dare || hd.wterm_per_traj)) || (hd.wterm_per_traj && !hd.wterm_from_dare))
       FAIL(-3, "kmpc_state_import: inconsistent header (terminal blocks)");
     if (hd.wterm_from_dare && sizeof(T) != 8) FAIL(-3, "kmpc_state_import: Riccati terminal blocks need a float64 handle");
-    const int64_t wb = !hd.have_wterm ? 0 : (hd.wterm_from_dare ? (int64_t)sizeof(double) : (int64_t)sizeof(T)) * hd.wterm_blocks * q * q;
-    const int64_t sb = hd.has_shared ? (int64_t)sizeof(double) * gram_elems() + (int64_t)sizeof(T) * ((int64_t)L * p + (int64_t)n * L) : 0;
-    if (bytes < (int64_t)sizeof(BlobHeader) + (int64_t)sizeof(T) * base_elems() + sb + wb) FAIL(-3, "kmpc_state_import: buffer too small");
+    if (bytes < sections(hd).blob_bytes()) FAIL(-3, "kmpc_state_import: buffer too small");
     { int rc = sync_own(); if (rc) return rc; }
     dense_valid = true; img_valid = false;  // (the blob overwrites every dense block)
     { int rc = forget_tableaux(nullptr); if (rc) return rc; }
     if (hd.has_shared) { int rc = shared_alloc(); if (rc) return rc; }
     if (hd.have_wterm) {
-      if (hd.wterm_from_dare) {
-        if (dare_cap < hd.wterm_blocks) {
-          if (dDareP) (void)hipFree(dDareP);
-          if (dDareIt) (void)hipFree(dDareIt);
-          if (dWtB) (void)hipFree(dWtB);
-          dDareP = nullptr; dDareIt = nullptr; dWtB = nullptr; dare_cap = 0;
-          HIPCHK(hipMalloc(&dDareP, sizeof(double) * (size_t)hd.wterm_blocks * L * L));
-          HIPCHK(hipMalloc(&dDareIt, sizeof(int32_t) * (size_t)hd.wterm_blocks));
-          HIPCHK(hipMalloc(&dWtB, sizeof(double) * (size_t)hd.wterm_blocks * q * q));
-          dare_cap = hd.wterm_blocks;
-        }
-      } else if (!dWt) {
-        HIPCHK(hipMalloc(&dWt, sizeof(T) * (size_t)q * q));
-      }
+      if (hd.wterm_from_dare) { int rc = dare_buffers(hd.wterm_blocks); if (rc) return rc; }
+      else HIPCHK(dWt.ensure((size_t)q * q));
     }
-    struct { void* ptr; size_t bytes; } parts[] = {
-        {dP, sizeof(T) * (size_t)sP * B}, {dK, sizeof(T) * (size_t)sK * B}, {dQ, sizeof(T) * (size_t)sQ * B},
-        {dC, sizeof(T) * (size_t)sC * B}, {dPsi[cur ^ 1], sizeof(T) * (size_t)L * B}, {dWarm, sizeof(T) * (size_t)N * B},
-        {dUprev, sizeof(T) * (size_t)B},
-        {dGram, hd.has_shared ? sizeof(double) * (size_t)gram_elems() : 0}, {dKs, hd.has_shared ? sizeof(T) * (size_t)L * p : 0},
-        {dCs, hd.has_shared ? sizeof(T) * (size_t)n * L : 0},
-        {hd.have_wterm ? (hd.wterm_from_dare ? (void*)dWtB : (void*)dWt) : nullptr, (size_t)wb}};
-    for (auto& pt : parts) {
-      if (!pt.bytes) continue;
-      HIPCHK(hipMemcpy(pt.ptr, o, pt.bytes, hipMemcpyDefault));
-      o += pt.bytes;
+    const Sections t = sections(hd);  // (now that every section of the blob has its buffer)
+    for (int i = 0; i < t.n; ++i) {
+      HIPCHK(hipMemcpy(t.s[i].ptr, o, t.s[i].bytes(), hipMemcpyDefault));
+      o += t.s[i].bytes();
     }
     have_prev = hd.have_prev != 0;
     rls_fresh = hd.rls_fresh != 0;
@@ -1862,8 +1850,8 @@ int kmpc_solve_dare(const void* A, const void* B, const double* Q, double R, int
                     void* P, void* K, int32_t* iters, void* s) {
   if (nb == 0) return 0;
   if (!A || !B || !Q || !P || nb < 0 || L < 1 || L > 64 || maxiter < 1) return -3;
-  double* dQl = nullptr;
-  if (hipMalloc(&dQl, sizeof(double) * (size_t)L * L) != hipSuccess) return -1001;
+  DevBuf<double> dQl;
+  if (dQl.alloc((size_t)L * L) != hipSuccess) return -1001;
   int rc = 0;
   if (hipMemcpyAsync(dQl, Q, sizeof(double) * (size_t)L * L, hipMemcpyHostToDevice, (hipStream_t)s) != hipSuccess) rc = -1002;
   DareArgs d{};
@@ -1874,7 +1862,6 @@ int kmpc_solve_dare(const void* A, const void* B, const double* Q, double R, int
   d.P = (double*)P; d.K = (double*)K; d.PN = nullptr; d.pn_sub_diag = 0.0; d.iters = iters;
   if (!rc && launch_dare(d, (hipStream_t)s) != hipSuccess) rc = -1003;
   if (hipStreamSynchronize((hipStream_t)s) != hipSuccess && !rc) rc = -1004;
-  (void)hipFree(dQl);
   return rc;
 }
 int kmpc_set_terminal_refresh(kmpc_handle* h, int every, const double* Q, double R, int maxiter, double eps) { NN(h); return h->set_terminal_refresh(every, Q, R, maxiter, eps); }
