@@ -149,6 +149,14 @@ template <int OPT> struct RoOpt {
 #define KMPC_RO_LB 7
 #endif
   static constexpr int LB = D ? (KMPC_RO_LB) : 0;
+  // How the vector of a row product reaches the two 16-lane rows of a half (half_gather / lds_row_dot below).  The generic kernels exchange
+  // registers at every site; the default-option kernel reads it back from LDS where that was measured a gain (profiles/lds_gather.txt):
+  //   LG_CHAIN  condensed-QP recursion of step_v2: v0 / v1 come from where every lane stores its element of the step anyway
+  enum { LG_CHAIN = 1 };
+#ifndef KMPC_RO_LG
+#define KMPC_RO_LG 1
+#endif
+  static constexpr int LG = D ? (KMPC_RO_LG) : 0;
   // first / last step of a launch (StepVar::step_k, launch_steps)
   template <typename SV> static __device__ __forceinline__ bool launch_first(const SV& sv) {
     int k = sv.step_k; asm volatile("" : "+s"(k)); return k == 0;
@@ -362,6 +370,48 @@ __device__ __forceinline__ void half_gather(double a, double& v0, double& v1) {
   const auto rh = __builtin_amdgcn_permlane16_swap(hi, hi, false, false);
   v0 = __hiloint2double(rh[0], rl[0]);
   v1 = __hiloint2double(rh[1], rl[1]);
+}
+// The same hand-over THROUGH LDS (default-option roll-out, RoOpt::LG): lane `tid` of the wave has stored its element at slot[tid]; a reader
+// gets v0 = slot[32 half + (t & 15)] and v1 = slot[32 half + 16 + (t & 15)] with two ds_read_b64 from ONE lane address (lds_gather_addr) and
+// immediate offsets -- no vector instruction, where half_gather is two moves, two swaps and their wait states.  The LDS queue of a wave is
+// in order, so the reads see a store the same wave issued before them: one s_waitcnt in front of the first reader, no barrier.  The 16
+// lanes of a row read 128 contiguous bytes, the two rows of a half the same addresses (a broadcast), lanes l and l + 32 never conflict.
+// The reads, their wait and the product that consumes them are ONE statement: the compiler does not count a load inside a statement, and
+// nothing of its own (a copy of v0, a spill) can come between the data's arrival and the DPP reads.  What LDS returns is not a VALU write
+// of the DPP source, so the product carries no `s_nop 1` here (the hazard row_dot_block pads is VALU write -> DPP read only); a register the
+// compiler wrote in front of the statement -- the accumulator's start value, the address -- is three instructions old at the first DPP read.
+__device__ __forceinline__ unsigned lds_gather_addr(const double* slot, int tid) {
+  return (unsigned)(size_t)(const lds_f64*)(slot + (tid & 47));
+}
+template <int CNT, int OFF> constexpr RowAsm lds_row_dot_text() {
+  RowAsm t{};
+  auto put = [&t](const char* p) { while (*p) t.s[t.n++] = *p++; };
+  auto num = [&t](int v) {
+    char d[8] = {}; int k = 0;
+    do { d[k++] = (char)('0' + v % 10); v /= 10; } while (v);
+    while (k) t.s[t.n++] = d[--k];
+  };
+  put("ds_read_b64 %1, %3 offset:"); num(OFF * 8); put("\n\tds_read_b64 %2, %3 offset:"); num((OFF + 16) * 8);
+  put("\n\ts_waitcnt lgkmcnt(0)");
+  for (int l = 0; l < CNT; ++l) {
+    put("\n\tv_fmac_f64_dpp %0, %"); num(l < 16 ? 1 : 2); put(", %"); num(4 + l);
+    put(" row_newbcast:"); num(l & 15); put(" row_mask:0xf bank_mask:0xf");
+  }
+  return t;
+}
+// ac += R[l] * vec[l], l < CNT, vec = the vector the wave stored at the slot of `addr`, OFF elements further on
+template <int CNT, int OFF, int NCOL>
+__device__ __forceinline__ void lds_row_dot(double& ac, unsigned addr, const double (&R)[NCOL]) {
+  static_assert(CNT > 16 && CNT <= 24 && CNT <= NCOL && OFF >= 0 && (OFF + 16) * 8 < 65536, "lds_row_dot: columns / offset");
+  double v0, v1;
+#define KMPC_RC(i) "v"(R[(i) < CNT ? (i) : 0])
+#define KMPC_RC4(i) KMPC_RC(i), KMPC_RC(i + 1), KMPC_RC(i + 2), KMPC_RC(i + 3)
+#define KMPC_DOT(...) asm volatile((lds_row_dot_text<CNT, OFF>()) : "+v"(ac), "=&v"(v0), "=&v"(v1) : "v"(addr), __VA_ARGS__ : "memory")
+  if constexpr (CNT <= 20) KMPC_DOT(KMPC_RC4(0), KMPC_RC4(4), KMPC_RC4(8), KMPC_RC4(12), KMPC_RC4(16));
+  else KMPC_DOT(KMPC_RC4(0), KMPC_RC4(4), KMPC_RC4(8), KMPC_RC4(12), KMPC_RC4(16), KMPC_RC4(20));
+#undef KMPC_DOT
+#undef KMPC_RC4
+#undef KMPC_RC
 }
 
 // ---- wave-wide sum on DPP (no LDS crossbar): Hillis-Steele prefix inside each 16-lane row with

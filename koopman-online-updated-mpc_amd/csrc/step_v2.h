@@ -12,7 +12,9 @@
 // (row_newbcast broadcasts element j of the regressor / of P z inside each 16-lane row; the vector itself is handed
 // to every row of a half with one v_permlane16_swap per dword): M z, the rank-one downdates and the gain updates of
 // duffing.py:927-953 are 2 x 21 + 21 + 21 + 20 instructions on full waves, and no element of the state passes through
-// LDS.  The layer-1 registers then ARE the rows of [A; C_o] the condensed-QP recursion needs (v chain in lanes 0-31,
+// LDS.  (What does pass through LDS in the default-option roll-out is a product VECTOR, not the state: the recursion of phase 2
+// reads v0 / v1 of its next product back from where every lane stores its element of the step anyway -- RoOpt::LG_CHAIN,
+// profiles/lds_gather.txt.)  The layer-1 registers then ARE the rows of [A; C_o] the condensed-QP recursion needs (v chain in lanes 0-31,
 // w chain in lanes 32-63), so the model is never re-read either.  In HBM a trajectory's state is the image of these
 // registers ("wave image"): [column pair][slot][2] doubles, a wave reads or writes 16 bytes per lane, fully coalesced
 // (v2_* below; kmpc_* entry points that want the dense row-major blocks convert, aux_kernels.hip).
@@ -323,8 +325,14 @@ __device__ __forceinline__ void step_v2(const StepArgs<double>& a, const StepVar
   // =====================================================================================
   {
     const bool isA = t < L_;
+    // Default-option roll-out (RoOpt::LG_CHAIN): the vector of the next product is read back from LDS.  Its elements are the values of
+    // the lanes t < L, and those all store at dump + tid + j q (an output row is a row of C: t >= L), so the product of step j reads
+    // v0 / v1 from the place step j - 1 stored to -- step_body.h lds_row_dot: no exchange of registers, 4 vector instructions and 3
+    // wait states less per step of the recursion.  The initial vector takes the same route through the place of step 0.
+    constexpr bool LGC = (O::LG & O::LG_CHAIN) != 0 && v2_chain_dump(N_) && L_ > 16 && L_ <= 24;  // (two rows of elements, one statement's operands)
     double v0, v1;
-    gather_rows<S1>(isA ? (half ? psin : R1[L_]) : 0.0, v0, v1);
+    if constexpr (LGC) lds_st(dump + tid, isA ? (half ? psin : R1[L_]) : 0.0);
+    else gather_rows<S1>(isA ? (half ? psin : R1[L_]) : 0.0, v0, v1);
     // delta-u form (Tank_System.m:110-113): x+ = A x + B s, s = 1 on the v chain and u_prev on the w chain
     const double bs = (O::du_mode(a) && isA) ? R1[L_] * (half ? up : 1.0) : 0.0;
     // the rows of C_o give g_j = C_o v_j and C_o w_j at step j (j = 0 .. N)
@@ -333,13 +341,24 @@ __device__ __forceinline__ void step_v2(const StepArgs<double>& a, const StepVar
     double* const optr = isO ? (half ? sEr - q + ro : sG + ro) : dump + tid;
     KTRACE(5);
     constexpr int JN = N_;
+    if constexpr (LGC) {
+      static_assert(JN * Q_ + 64 <= 64 + (N_ + 1) * Q_, "step_v2: the recursion's reads stay inside the dump area");
+      const unsigned ga = lds_gather_addr(dump, tid);
+      static_for<0, JN + 1>([&](auto JJ) {
+        constexpr int j = decltype(JJ)::value;
+        double acc = bs;
+        lds_row_dot<L_, (j > 0 ? j - 1 : 0) * Q_>(acc, ga, R1);
+        optr[j * q] = acc;
+      });
+    } else {
 #pragma unroll
-    for (int j = 0; j <= JN; ++j) {
-      double acc = bs;
-      rowdot_one<L_, NC>(acc, v0, v1, R1);
-      if constexpr (v2_chain_dump(N_)) optr[j * q] = acc;
-      else if (isO) optr[j * q] = acc;
-      if (j < JN) gather_rows<S1>(acc, v0, v1);
+      for (int j = 0; j <= JN; ++j) {
+        double acc = bs;
+        rowdot_one<L_, NC>(acc, v0, v1, R1);
+        if constexpr (v2_chain_dump(N_)) optr[j * q] = acc;
+        else if (isO) optr[j * q] = acc;
+        if (j < JN) gather_rows<S1>(acc, v0, v1);
+      }
     }
     block_sync<64>();
     // e_j = C_o w_j - r_{j-1}
