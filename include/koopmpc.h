@@ -332,6 +332,35 @@ int64_t kmpc_state_bytes(const kmpc_handle* h);
 int kmpc_state_export(kmpc_handle* h, void* host_blob, int64_t bytes);
 int kmpc_state_import(kmpc_handle* h, const void* host_blob, int64_t bytes);
 
+/* ---- trajectories between handles of any batch size, on the device ----------------------- */
+/* A packed row is ONE trajectory's share of the per-trajectory sections of the blob, in the blob's order and the handle's dtype T:
+ *   P[sP] K[sK] Q[sQ] C[sC] psi_prev[L] warm[N] u_prev[1], then have_prev and rls_fresh as 0 or 1 in T, then zero padding up to a
+ * multiple of 16 bytes (sP .. sC: the full even strides of the blob, padding element included; warm: the trajectory's column of the
+ * [N][B] panel).  The bytes of a row's segments equal the bytes of the blob's sections for that trajectory.
+ * Elements of one row; -3 for a handle the row calls do not support (below).                                                        */
+int64_t kmpc_state_row_elems(const kmpc_handle* h);
+/* rows_dev[count][row_elems] <- the trajectories idx_dev[0 .. count) of the handle (device int32; NULL: 0 .. count-1); an index may
+ * appear more than once.  A synchronisation point for the handle exactly as kmpc_state_export is (a float32 handle continues from its
+ * rounded float32 blocks).  Returns when the copy is enqueued on `stream` and the index check has been read back.                   */
+int kmpc_state_pack(kmpc_handle* h, const int32_t* idx_dev, int count, void* rows_dev, void* stream);
+/* trajectories idx_dev[0 .. count) of the handle <- rows_dev[count][row_elems]; no trajectory may be named twice, count <= batch.
+ * have_prev and rls_fresh belong to the handle, not to a trajectory: every row's two flag elements must equal the handle's -- except in
+ * a call that fills the whole handle (idx_dev == NULL, count == batch) with rows that all carry the same pair, which the handle then
+ * adopts (a fresh handle takes over part of a running one).  The trajectories that are not named keep their state.                  */
+int kmpc_state_unpack(kmpc_handle* h, const int32_t* idx_dev, int count, const void* rows_dev, void* stream);
+/* kmpc_state_pack of src's trajectories src_idx_dev into rows that dst owns, then kmpc_state_unpack into dst's dst_idx_dev: with
+ * src == dst and overlapping lists every destination receives what its source held BEFORE the call.  -3 unless n, L, N, dtype,
+ * output_kind and the output rows of the two handles agree (batch, plant, bounds and weights need not).
+ * All three: count == 0 succeeds and does nothing.  A small kernel validates the indices (range; duplicates on a destination) and the
+ * rows' flags before any copy is launched: -3, kmpc_last_error names which, and the destination is unchanged; no index is ever
+ * followed out of bounds.
+ * Out of scope, -3 on every one of the four calls: a handle that has its shared-model blocks (after kmpc_shared_local_gram /
+ * kmpc_shared_solve / kmpc_shared_rollout: its model is pooled over the batch, a trajectory has no state of its own), and a handle with
+ * per-trajectory terminal blocks (kmpc_terminal_from_dare with per_trajectory = 1, or kmpc_set_terminal_refresh armed).  ONE shared
+ * terminal block (kmpc_set_terminal_weight) stays with its handle like any other setting and is no part of a row.                   */
+int kmpc_state_transfer(kmpc_handle* dst, const int32_t* dst_idx_dev, kmpc_handle* src, const int32_t* src_idx_dev, int count,
+                        void* stream);
+
 /* ---- measurement ------------------------------------------------------------------------ */
 /* when enabled, kmpc_step brackets its kernels with HIP events on `stream`                  */
 int kmpc_profile_enable(kmpc_handle* h, int on);

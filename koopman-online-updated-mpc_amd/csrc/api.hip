@@ -11,6 +11,7 @@
 #include "../../include/koopmpc.h"
 #include "devbuf.h"
 #include "kernels.h"
+#include "state_rows.h"
 #include <dlfcn.h>
 #include <rccl/rccl.h>  // types and enumerators only (ncclDouble, ncclSum): the library resolves ncclAllReduce at run time
 
@@ -20,7 +21,7 @@ static thread_local std::string g_create_error;
 
 struct kmpc_handle {
   kmpc_config cfg{};
-  std::string err;
+  mutable std::string err;
   virtual ~kmpc_handle() {
     for (auto& mk : marks) (void)hipEventDestroy(mk.e);
   }
@@ -118,6 +119,10 @@ struct kmpc_handle {
   virtual int64_t state_bytes() const = 0;
   virtual int state_export(void* blob, int64_t bytes) = 0;
   virtual int state_import(const void* blob, int64_t bytes) = 0;
+  virtual int64_t state_row_elems() const = 0;
+  virtual int state_pack(const int32_t* idx, int count, void* rows, hipStream_t s) = 0;
+  virtual int state_unpack(const int32_t* idx, int count, const void* rows, hipStream_t s) = 0;
+  virtual int state_transfer(const int32_t* dst_idx, kmpc_handle* src, const int32_t* src_idx, int count, hipStream_t s) = 0;
   virtual int profile_enable(int on) = 0;
   virtual int profile_read(double* ms2, int64_t* count, int reset) = 0;
   virtual int64_t algorithmic_bytes() const = 0;
@@ -204,17 +209,22 @@ struct BlobHeader {
   double P0, barQ0;
 };
 static_assert(sizeof(BlobHeader) == 80, "BlobHeader is the first 80 bytes of a state blob");
-// one section of a blob as a handle holds it, and the ordered list of them (Impl::sections)
-struct Section {
-  void* ptr; size_t elem, count;  // element size, elements
-  size_t bytes() const { return elem * count; }
-};
-struct Sections {
-  Section s[11];
-  int n = 0, n_traj = 0;  // n_traj: the leading sections that hold per-trajectory state (P .. u_prev)
-  void add(void* ptr, size_t elem, size_t count) { s[n++] = Section{ptr, elem, count}; }
-  int64_t blob_bytes() const { int64_t b = sizeof(BlobHeader); for (int i = 0; i < n; ++i) b += (int64_t)s[i].bytes(); return b; }
-};
+// (Section / Sections, one section of a blob as a handle holds it and the ordered list of them: csrc/state_rows.h)
+static inline int64_t blob_bytes(const Sections& t) { return (int64_t)sizeof(BlobHeader) + t.payload_bytes(); }
+//
+// ---- The packed row of kmpc_state_pack / kmpc_state_unpack / kmpc_state_transfer: ONE trajectory's share of the leading n_traj
+// sections above, in the blob's order and the handle's dtype T.  This comment is the format; build_row_plan (csrc/state_rows.h) derives
+// it from Impl::sections() and tests/test_gpu_state_rows.py holds the bytes to the blob's.
+//
+//   P[sP] K[sK] Q[sQ] C[sC]   the trajectory's full strides, padding element included
+//   psi_prev[L]
+//   warm[N]                   the trajectory's column of the [N][B] panel
+//   u_prev[1]
+//   have_prev, rls_fresh      the handle's two flags, 0 or 1 as T
+//   zero padding              up to row_elems = the next multiple of 16 bytes
+//
+// rows_dev of the three calls is [count][row_elems], trajectory-major.  The bytes of a row's segments equal the bytes of the blob's
+// sections for that trajectory.
 
 template <typename T>
 struct Impl : kmpc_handle {
@@ -1657,14 +1667,14 @@ struct Impl : kmpc_handle {
     Sections t;
     t.add(dP, sizeof(T), (size_t)sP * B); t.add(dK, sizeof(T), (size_t)sK * B);
     t.add(dQ, sizeof(T), (size_t)sQ * B); t.add(dC, sizeof(T), (size_t)sC * B);
-    t.add(dPsi[cur ^ 1], sizeof(T), (size_t)L * B); t.add(dWarm, sizeof(T), (size_t)N * B); t.add(dUprev, sizeof(T), (size_t)B);
+    t.add(dPsi[cur ^ 1], sizeof(T), (size_t)L * B); t.add(dWarm, sizeof(T), (size_t)N * B, (size_t)N); t.add(dUprev, sizeof(T), (size_t)B);
     t.n_traj = t.n;
     if (hd.has_shared) { t.add(dGram, sizeof(double), (size_t)gram_elems()); t.add(dKs, sizeof(T), (size_t)L * p); t.add(dCs, sizeof(T), (size_t)n * L); }
     if (hd.have_wterm && hd.wterm_from_dare) t.add(dWtB, sizeof(double), (size_t)hd.wterm_blocks * q * q);
     else if (hd.have_wterm) t.add(dWt, sizeof(T), (size_t)hd.wterm_blocks * q * q);
     return t;
   }
-  int64_t state_bytes() const override { return sections(blob_header()).blob_bytes(); }
+  int64_t state_bytes() const override { return blob_bytes(sections(blob_header())); }
   int state_export(void* blob, int64_t bytes) override {
     if (bytes < state_bytes() || !blob) FAIL(-3, "kmpc_state_export: buffer too small");
     { int rc = sync_own(); if (rc) return rc; }  // (a roll-out on a non-blocking stream may still be writing the wave image)
@@ -1700,7 +1710,7 @@ struct Impl : kmpc_handle {
         (!hd.have_wterm && (hd.wterm_from_dare || hd.wterm_per_traj)) || (hd.wterm_per_traj && !hd.wterm_from_dare))
       FAIL(-3, "kmpc_state_import: inconsistent header (terminal blocks)");
     if (hd.wterm_from_dare && sizeof(T) != 8) FAIL(-3, "kmpc_state_import: Riccati terminal blocks need a float64 handle");
-    if (bytes < sections(hd).blob_bytes()) FAIL(-3, "kmpc_state_import: buffer too small");
+    if (bytes < blob_bytes(sections(hd))) FAIL(-3, "kmpc_state_import: buffer too small");
     { int rc = sync_own(); if (rc) return rc; }
     dense_valid = true; img_valid = false;  // (the blob overwrites every dense block)
     { int rc = forget_tableaux(nullptr); if (rc) return rc; }
@@ -1751,6 +1761,100 @@ struct Impl : kmpc_handle {
       return core_weight(&w);
     }
     return core_weight(nullptr);
+  }
+
+  // ---- packed rows: trajectories in and out of the handle on the device (the row format: the comment behind BlobHeader)
+  DevBuf<int32_t> dRowChk;  // [B] marks of the duplicate check, then the status word of state_rows_check_kernel
+  DevBuf<T> dRowStage;      // kmpc_state_transfer into this handle: the packed rows between gather and scatter, grown on demand
+  // a trajectory of this handle has state of its own that a row carries whole
+  bool rows_supported(const char* who) const {
+    if (dGram) { err = std::string(who) + ": the handle has its shared-model blocks -- the model is pooled over the batch, a trajectory has no state of its own"; return false; }
+    if ((have_wterm && wterm_from_dare && wterm_per_traj) || term_every > 0) {
+      err = std::string(who) + ": per-trajectory terminal blocks (kmpc_terminal_from_dare per trajectory, kmpc_set_terminal_refresh) are no part of a packed row";
+      return false;
+    }
+    return true;
+  }
+  // the one layout of a row: derived from the list of state blocks
+  bool row_plan(RowPlan* pl) const { return build_row_plan(sections(blob_header()), B, pl); }
+  int64_t state_row_elems() const override {
+    RowPlan pl;
+    if (!rows_supported("kmpc_state_row_elems")) return -3;
+    if (!row_plan(&pl)) { err = "kmpc_state_row_elems: no row layout for this handle"; return -3; }
+    return pl.row_elems;
+  }
+  // runs the check kernel on s and reads its word back: 0, or -3 with the message; *word: the status (the flags of row 0)
+  int rows_check(const char* who, const RowPlan& pl, const int32_t* idx, int count, bool dup, const void* rows, int want_hp, int want_rf, int* word,
+                 hipStream_t s) {
+    HIPCHK(dRowChk.ensure((size_t)B + 1));
+    int32_t* const status = dRowChk.get() + B;
+    HIPCHK(launch_state_rows_check(idx, count, B, dup ? dRowChk.get() : nullptr, rows, pl, want_hp, want_rf, status, s));
+    int32_t w = 0;
+    HIPCHK(hipMemcpyAsync(&w, status, sizeof(w), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    if (word) *word = w;
+    if (w & ROWS_BAD_RANGE) FAIL(-3, std::string(who) + ": a trajectory index lies outside [0, batch)");
+    if (w & ROWS_BAD_DUP) FAIL(-3, std::string(who) + ": a destination trajectory is named twice");
+    if (w & ROWS_BAD_FLAG_VALUE) FAIL(-3, std::string(who) + ": a row's have_prev / rls_fresh elements are not 0 or 1");
+    if (w & ROWS_BAD_FLAG_MIXED)
+      FAIL(-3, std::string(who) + (want_hp < 0 ? ": the rows carry different have_prev / rls_fresh flags" : ": the rows' have_prev / rls_fresh flags are not the handle's (only a call that fills the whole handle adopts them)"));
+    return 0;
+  }
+  int state_pack(const int32_t* idx, int count, void* rows, hipStream_t s) override {
+    if (count < 0 || (count > 0 && !rows)) FAIL(-3, "kmpc_state_pack: bad arguments");
+    if (!rows_supported("kmpc_state_pack")) return -3;
+    if (count == 0) return 0;
+    { int rc = sync_own(); if (rc) return rc; }
+    RowPlan pl;
+    if (!row_plan(&pl)) FAIL(-3, "kmpc_state_pack: no row layout for this handle");
+    if (idx) { int rc = rows_check("kmpc_state_pack", pl, idx, count, false, nullptr, 0, 0, nullptr, s); if (rc) return rc; }
+    else if (count > B) FAIL(-3, "kmpc_state_pack: count exceeds the batch (no index list)");
+    // a synchronisation point for the source, as kmpc_state_export is
+    { int rc = ensure_dense(s, false); if (rc) return rc; }
+    { int rc = forget_tableaux(s); if (rc) return rc; }
+    if (core) img_valid = false;  // (a float32 handle continues from its rounded float32 blocks, as the receiver of the rows will)
+    HIPCHK(launch_state_rows_gather<T>(pl, idx, count, B, (T*)rows, have_prev ? 1 : 0, rls_fresh ? 1 : 0, s));
+    return 0;
+  }
+  int state_unpack(const int32_t* idx, int count, const void* rows, hipStream_t s) override {
+    if (count < 0 || (count > 0 && !rows)) FAIL(-3, "kmpc_state_unpack: bad arguments");
+    if (count > B) FAIL(-3, "kmpc_state_unpack: more rows than the handle has trajectories");
+    if (!rows_supported("kmpc_state_unpack")) return -3;
+    if (count == 0) return 0;
+    { int rc = sync_own(); if (rc) return rc; }
+    RowPlan pl;
+    if (!row_plan(&pl)) FAIL(-3, "kmpc_state_unpack: no row layout for this handle");
+    // the flags belong to the handle: every row must carry its pair, except that a call which fills the whole handle brings its own
+    const bool whole = !idx && count == B;
+    int word = 0;
+    { int rc = rows_check("kmpc_state_unpack", pl, idx, count, idx != nullptr, rows, whole ? -1 : (have_prev ? 1 : 0), whole ? -1 : (rls_fresh ? 1 : 0), &word, s);
+      if (rc) return rc; }
+    { int rc = ensure_dense(s, true); if (rc) return rc; }  // (first: the trajectories the call leaves alone must be valid in the dense blocks)
+    HIPCHK(launch_state_rows_scatter<T>(pl, idx, count, B, (const T*)rows, s));
+    dense_valid = true; img_valid = false;
+    { int rc = forget_tableaux(s); if (rc) return rc; }
+    if (whole) { have_prev = (word & ROWS_ROW0_HAVE_PREV) != 0; rls_fresh = (word & ROWS_ROW0_RLS_FRESH) != 0; }
+    return 0;
+  }
+  int state_transfer(const int32_t* dst_idx, kmpc_handle* src_h, const int32_t* src_idx, int count, hipStream_t s) override {
+    if (!src_h || count < 0) FAIL(-3, "kmpc_state_transfer: bad arguments");
+    const kmpc_config& sc = src_h->cfg;
+    if (sc.dtype != cfg.dtype || sc.n != n || sc.L != L || sc.N != N || sc.output_kind != cfg.output_kind || src_h->device != device)
+      FAIL(-3, "kmpc_state_transfer: the handles differ in n, L, N, dtype, output kind or device");
+    Impl<T>* const src = static_cast<Impl<T>*>(src_h);  // (same dtype: the same instantiation)
+    if (src->q != q || (cfg.output_kind != KMPC_OUT_LIFT && sc.out_row0 != cfg.out_row0)) FAIL(-3, "kmpc_state_transfer: the handles differ in their output rows");
+    if (count > B) FAIL(-3, "kmpc_state_transfer: more rows than the destination has trajectories");
+    if (!rows_supported("kmpc_state_transfer (destination)")) return -3;
+    if (!src->rows_supported("kmpc_state_transfer (source)")) { err = src->err; return -3; }
+    if (count == 0) return 0;
+    // gather into this handle's staging rows, then scatter: with src == dst and overlapping lists every destination receives what its
+    // source held before the call
+    RowPlan pl;
+    if (!row_plan(&pl)) FAIL(-3, "kmpc_state_transfer: no row layout for this handle");
+    { int rc = sync_own(); if (rc) return rc; }  // (the staging rows may still be read by an earlier transfer on another stream)
+    HIPCHK(dRowStage.grow((size_t)count * pl.row_elems));
+    { const int rc = src->state_pack(src_idx, count, dRowStage.get(), s); if (rc) { err = "kmpc_state_transfer, source: " + src->err; return rc; } }
+    return state_unpack(dst_idx, count, dRowStage.get(), s);
   }
 
   int profile_enable(int on) override {
@@ -1992,6 +2096,15 @@ int kmpc_shared_rollout(kmpc_handle* h, int plant, void* X, const void* ref, int
 int64_t kmpc_state_bytes(const kmpc_handle* h) { return h ? h->state_bytes() : -1; }
 int kmpc_state_export(kmpc_handle* h, void* blob, int64_t bytes) { NN(h); return h->state_export(blob, bytes); }
 int kmpc_state_import(kmpc_handle* h, const void* blob, int64_t bytes) { NN(h); return h->state_import(blob, bytes); }
+int64_t kmpc_state_row_elems(const kmpc_handle* h) { return h ? h->state_row_elems() : -1; }
+int kmpc_state_pack(kmpc_handle* h, const int32_t* idx, int count, void* rows, void* s) { NNS(h, s); return h->state_pack(idx, count, rows, (hipStream_t)s); }
+int kmpc_state_unpack(kmpc_handle* h, const int32_t* idx, int count, const void* rows, void* s) { NNS(h, s); return h->state_unpack(idx, count, rows, (hipStream_t)s); }
+int kmpc_state_transfer(kmpc_handle* dst, const int32_t* dst_idx, kmpc_handle* src, const int32_t* src_idx, int count, void* s) {
+  NNS(dst, s);
+  if (!src) return -1;
+  StreamMarkAtExit mark_src{src, (hipStream_t)s};  // (the source's gather runs on this stream too)
+  return dst->state_transfer(dst_idx, src, src_idx, count, (hipStream_t)s);
+}
 int kmpc_profile_enable(kmpc_handle* h, int on) { NN(h); return h->profile_enable(on); }
 int kmpc_profile_read(kmpc_handle* h, double* ms2, int64_t* count, int reset) { NN(h); return h->profile_read(ms2, count, reset); }
 int64_t kmpc_algorithmic_bytes_per_step(const kmpc_handle* h) { return h ? h->algorithmic_bytes() : -1; }

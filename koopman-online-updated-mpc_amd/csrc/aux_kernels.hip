@@ -9,6 +9,7 @@
 #include "kernels.h"
 #include <cstdlib>
 #include "plant_device.h"
+#include "state_rows.h"
 
 namespace kmpc {
 
@@ -460,5 +461,117 @@ template <typename T> hipError_t launch_pack_afrag(const T* src, int Mp, int Hp,
 }
 template hipError_t launch_pack_afrag<float>(const float*, int, int, int, float*, hipStream_t);
 template hipError_t launch_pack_afrag<double>(const double*, int, int, int, double*, hipStream_t);
+
+// ---------------------------------------------------------------------------------------
+// Packed rows of per-trajectory state (kmpc_state_pack / _unpack / _transfer; the row format: api.hip, the plan: state_rows.h).
+// Pure data movement.  state_rows_check_kernel runs first and alone decides whether a call is valid; the copy kernels skip an index
+// outside [0, B) on their own account all the same.
+// ---------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void state_rows_check_kernel(const int32_t* __restrict__ idx, int count, int B, int32_t* __restrict__ mark,
+                                                               const char* __restrict__ rows, int elem, long row_elems, int flag_off,
+                                                               int want_hp, int want_rf, int32_t* __restrict__ status) {
+  // a flag element as an integer: 0 / 1, anything else -1
+  auto flag_at = [&](long r, int k) -> int {
+    const char* const e = rows + ((size_t)r * row_elems + flag_off + k) * elem;
+    const double v = elem == 8 ? *reinterpret_cast<const double*>(e) : (double)*reinterpret_cast<const float*>(e);
+    return v == 0.0 ? 0 : (v == 1.0 ? 1 : -1);
+  };
+  int hp0 = want_hp, rf0 = want_rf;
+  if (rows && (want_hp < 0 || want_rf < 0)) { hp0 = flag_at(0, 0); rf0 = flag_at(0, 1); }  // (every thread reads row 0: one cached line)
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < count; i += (long)gridDim.x * 256) {
+    const int b = idx ? idx[i] : (int)i;
+    int bad = 0;
+    if (b < 0 || b >= B) bad |= ROWS_BAD_RANGE;
+    else if (mark && atomicAdd(&mark[b], 1) != 0) bad |= ROWS_BAD_DUP;
+    if (rows) {
+      const int hp = flag_at(i, 0), rf = flag_at(i, 1);
+      if (hp < 0 || rf < 0) bad |= ROWS_BAD_FLAG_VALUE;
+      else if (hp != hp0 || rf != rf0) bad |= ROWS_BAD_FLAG_MIXED;
+      if (i == 0) bad |= (hp == 1 ? ROWS_ROW0_HAVE_PREV : 0) | (rf == 1 ? ROWS_ROW0_RLS_FRESH : 0);
+    }
+    if (bad) atomicOr(status, bad);
+  }
+}
+hipError_t launch_state_rows_check(const int32_t* idx, int count, int B, int32_t* mark, const void* rows, const RowPlan& pl, int want_hp, int want_rf,
+                                   int32_t* status, hipStream_t s) {
+  if (count <= 0 || B <= 0 || !status) return hipErrorInvalidValue;
+  hipError_t e = hipMemsetAsync(status, 0, sizeof(int32_t), s);
+  if (e == hipSuccess && mark) e = hipMemsetAsync(mark, 0, sizeof(int32_t) * (size_t)B, s);
+  if (e != hipSuccess) return e;
+  const int grid = (count + 255) / 256;
+  hipLaunchKernelGGL(state_rows_check_kernel, dim3(grid > 2048 ? 2048 : grid), dim3(256), 0, s, idx, count, B, mark, (const char*)rows, pl.elem,
+                     (long)pl.row_elems, pl.flag_off, want_hp, want_rf, status);
+  return hipGetLastError();
+}
+
+// len contiguous elements by the whole workgroup: 16-byte vectors where both sides are 16-byte aligned (every float64 segment: the
+// even_up strides), 8-byte ones where both are 8-byte aligned (float32 segments), element by element otherwise; the tail likewise
+typedef unsigned int rows_v4 __attribute__((ext_vector_type(4)));
+typedef unsigned int rows_v2 __attribute__((ext_vector_type(2)));
+template <typename T> __device__ __forceinline__ void rows_copy_contig(T* __restrict__ dst, const T* __restrict__ src, int len, int tid) {
+  const uintptr_t a = (uintptr_t)dst | (uintptr_t)src;  // (wave-uniform: the trajectory index is)
+  int done = 0;
+  if ((a & 15) == 0) {
+    constexpr int V = 16 / (int)sizeof(T);
+    const int nv = len / V;
+    for (int i = tid; i < nv; i += 256) reinterpret_cast<rows_v4*>(dst)[i] = reinterpret_cast<const rows_v4*>(src)[i];
+    done = nv * V;
+  } else if (sizeof(T) == 4 && (a & 7) == 0) {
+    const int nv = len / 2;
+    for (int i = tid; i < nv; i += 256) reinterpret_cast<rows_v2*>(dst)[i] = reinterpret_cast<const rows_v2*>(src)[i];
+    done = nv * 2;
+  }
+  for (int i = done + tid; i < len; i += 256) dst[i] = src[i];
+}
+// one workgroup per packed row.  PACK: row <- trajectory, else trajectory <- row.
+template <typename T, bool PACK>
+__device__ __forceinline__ void state_rows_move(const RowPlan& pl, const int32_t* __restrict__ idx, int B, T* __restrict__ rows, T hp, T rf) {
+  const int r = blockIdx.x, tid = threadIdx.x;
+  const int b = __builtin_amdgcn_readfirstlane(idx ? idx[r] : r);  // read once, wave-uniform: every address below is base + lane offset
+  if (b < 0 || b >= B) return;
+  T* const row = rows + (size_t)r * pl.row_elems;
+  const int lane = tid - 192;  // the last wave also takes the strided column, the scalars and the padding
+  for (int k = 0; k < pl.nseg; ++k) {
+    const RowSeg& g = pl.seg[k];
+    T* const blk = reinterpret_cast<T*>(g.base) + (size_t)b * g.stride;
+    T* const in_row = row + g.off;
+    if (g.step == 1 && g.len > 1) {
+      if (PACK) rows_copy_contig<T>(in_row, blk, g.len, tid);
+      else rows_copy_contig<T>(blk, in_row, g.len, tid);
+    } else if (lane >= 0) {
+      for (int j = lane; j < g.len; j += 64) {
+        if (PACK) in_row[j] = blk[(size_t)j * g.step];
+        else blk[(size_t)j * g.step] = in_row[j];
+      }
+    }
+  }
+  if (PACK && lane >= 0)
+    for (int j = pl.flag_off + lane; j < pl.row_elems; j += 64) row[j] = j == pl.flag_off ? hp : (j == pl.flag_off + 1 ? rf : T(0));
+}
+template <typename T> __global__ __launch_bounds__(256) void state_rows_gather_kernel(const RowPlan pl, const int32_t* __restrict__ idx, int B, T* __restrict__ rows, T hp, T rf) {
+  state_rows_move<T, true>(pl, idx, B, rows, hp, rf);
+}
+template <typename T> __global__ __launch_bounds__(256) void state_rows_scatter_kernel(const RowPlan pl, const int32_t* __restrict__ idx, int B, const T* __restrict__ rows) {
+  state_rows_move<T, false>(pl, idx, B, const_cast<T*>(rows), T(0), T(0));
+}
+static bool rows_plan_ok(const RowPlan& pl, size_t elem) {
+  return pl.nseg >= 1 && pl.nseg <= RowPlan::kMaxSeg && (size_t)pl.elem == elem && pl.flag_off + 2 <= pl.row_elems;
+}
+template <typename T> hipError_t launch_state_rows_gather(const RowPlan& pl, const int32_t* idx, int count, int B, T* rows, int have_prev, int rls_fresh, hipStream_t s) {
+  if (count <= 0) return hipSuccess;
+  if (!rows || B <= 0 || !rows_plan_ok(pl, sizeof(T))) return hipErrorInvalidValue;
+  hipLaunchKernelGGL((state_rows_gather_kernel<T>), dim3(count), dim3(256), 0, s, pl, idx, B, rows, T(have_prev ? 1 : 0), T(rls_fresh ? 1 : 0));
+  return hipGetLastError();
+}
+template <typename T> hipError_t launch_state_rows_scatter(const RowPlan& pl, const int32_t* idx, int count, int B, const T* rows, hipStream_t s) {
+  if (count <= 0) return hipSuccess;
+  if (!rows || B <= 0 || !rows_plan_ok(pl, sizeof(T))) return hipErrorInvalidValue;
+  hipLaunchKernelGGL((state_rows_scatter_kernel<T>), dim3(count), dim3(256), 0, s, pl, idx, B, rows);
+  return hipGetLastError();
+}
+template hipError_t launch_state_rows_gather<float>(const RowPlan&, const int32_t*, int, int, float*, int, int, hipStream_t);
+template hipError_t launch_state_rows_gather<double>(const RowPlan&, const int32_t*, int, int, double*, int, int, hipStream_t);
+template hipError_t launch_state_rows_scatter<float>(const RowPlan&, const int32_t*, int, int, const float*, hipStream_t);
+template hipError_t launch_state_rows_scatter<double>(const RowPlan&, const int32_t*, int, int, const double*, hipStream_t);
 
 }  // namespace kmpc

@@ -3,7 +3,7 @@
 Host mirror of the reference's call surface over libkoopmpc.so (hand-written HIP, gfx950).
 """
 from . import _ffi  # noqa: F401
-from .sharding import shard_range, max_over_ranks  # noqa: F401
+from .sharding import shard_range, max_over_ranks, reshard_plan, regroup  # noqa: F401
 
 
 def __getattr__(name):

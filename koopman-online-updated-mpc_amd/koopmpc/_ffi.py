@@ -92,6 +92,10 @@ SIGNATURES = {
     "kmpc_state_bytes": (_I64, [_VP]),
     "kmpc_state_export": (_I, [_VP, _VP, _I64]),
     "kmpc_state_import": (_I, [_VP, _VP, _I64]),
+    "kmpc_state_row_elems": (_I64, [_VP]),
+    "kmpc_state_pack": (_I, [_VP, _VP, _I, _VP, _VP]),
+    "kmpc_state_unpack": (_I, [_VP, _VP, _I, _VP, _VP]),
+    "kmpc_state_transfer": (_I, [_VP, _VP, _VP, _VP, _I, _VP]),
     "kmpc_profile_enable": (_I, [_VP, _I]),
     "kmpc_profile_read": (_I, [_VP, _DP, C.POINTER(_I64), _I]),
     "kmpc_algorithmic_bytes_per_step": (_I64, [_VP]),

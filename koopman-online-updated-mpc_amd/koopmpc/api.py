@@ -638,6 +638,67 @@ class KoopmanMPC:
         buf = np.ascontiguousarray(sd["blob"], dtype=np.uint8)
         self._chk(self.lib.kmpc_state_import(self.h, C.c_void_p(buf.ctypes.data), buf.size), "kmpc_state_import")
 
+    # ------------------------------------------------------------------ trajectories between handles (packed rows)
+    def _idx(self, idx):
+        """list / numpy array / tensor of trajectory indices -> (contiguous int32 device tensor or None, count or None)"""
+        if idx is None:
+            return None, None
+        if not torch.is_tensor(idx):
+            idx = torch.as_tensor(np.asarray(idx, dtype=np.int64).reshape(-1))
+        if idx.dim() != 1:
+            raise ValueError("an index list must be one-dimensional")
+        idx = idx.to(device=self.device, dtype=torch.int32).contiguous()
+        return idx, int(idx.numel())
+
+    def state_row_elems(self):
+        """Elements of one packed row (kmpc_state_row_elems); raises for a handle the row calls do not support."""
+        ne = int(self.lib.kmpc_state_row_elems(self.h))
+        if ne < 0:
+            self._chk(ne, "kmpc_state_row_elems")
+        return ne
+
+    def pack_state(self, idx=None, out=None):
+        """The per-trajectory state of the trajectories `idx` (all of them, in order, when None; an index may repeat) as a device
+        tensor (count, row_elems) of the controller's dtype -- kmpc_state_pack; the row format is documented in include/koopmpc.h.
+        A synchronisation point exactly as state_dict() is.  `out`: a contiguous (count, row_elems) device tensor to fill."""
+        it, count = self._idx(idx)
+        count = self.B if it is None else count
+        ne = self.state_row_elems()
+        if out is None:
+            out = torch.empty(count, ne, dtype=self.dtype, device=self.device)
+        elif not (torch.is_tensor(out) and out.device == self.device and out.dtype == self.dtype and out.is_contiguous() and tuple(out.shape) == (count, ne)):
+            raise ValueError("out must be a contiguous (%d, %d) tensor of the controller's dtype and device" % (count, ne))
+        self._chk(self.lib.kmpc_state_pack(self.h, self._p(it) if it is not None else None, count, self._p(out), self._stream()), "kmpc_state_pack")
+        return out
+
+    def unpack_state(self, rows, idx=None):
+        """The rows of pack_state() into the trajectories `idx` (0 .. count-1 when None; none may repeat) -- kmpc_state_unpack.  The
+        rows' have_prev / rls_fresh flags must be this controller's, unless the call fills the whole controller (idx None and
+        count == batch): then it adopts them."""
+        it, count = self._idx(idx)
+        ne = self.state_row_elems()
+        if not torch.is_tensor(rows) or rows.dim() != 2 or rows.shape[1] != ne or rows.dtype != self.dtype or rows.device != self.device:
+            raise ValueError("rows must be a (count, %d) tensor of the controller's dtype and device" % ne)
+        if count is not None and count != rows.shape[0]:
+            raise ValueError("%d rows for %d indices" % (rows.shape[0], count))
+        if rows.shape[0] > self.B:
+            raise ValueError("%d rows for a batch of %d" % (rows.shape[0], self.B))
+        rows = rows.contiguous()
+        self._chk(self.lib.kmpc_state_unpack(self.h, self._p(it) if it is not None else None, int(rows.shape[0]), self._p(rows), self._stream()),
+                  "kmpc_state_unpack")
+
+    def transfer_state(self, src, src_idx=None, dst_idx=None):
+        """Trajectories `src_idx` of the controller `src` into the trajectories `dst_idx` of this one, on the device
+        (kmpc_state_transfer): both lists must have the same length; None stands for 0 .. count-1 (with both None: all of src's).
+        src may be this controller: every destination receives what its source held before the call."""
+        si, sc = src._idx(src_idx)
+        di, dc = self._idx(dst_idx)
+        if sc is not None and dc is not None and sc != dc:
+            raise ValueError("src_idx and dst_idx differ in length (%d, %d)" % (sc, dc))
+        count = sc if sc is not None else (dc if dc is not None else src.B)
+        self._chk(self.lib.kmpc_state_transfer(self.h, self._p(di) if di is not None else None, src.h, self._p(si) if si is not None else None,
+                                               int(count), self._stream()), "kmpc_state_transfer")
+
     # ------------------------------------------------------------------ measurement
     def profile(self, on=True):
         self._chk(self.lib.kmpc_profile_enable(self.h, int(on)), "kmpc_profile_enable")

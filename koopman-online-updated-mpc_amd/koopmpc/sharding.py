@@ -15,6 +15,50 @@ def shard_range(total, rank, world):
     return lo, lo + base + (1 if rank < rem else 0)
 
 
+def reshard_plan(total, old_world, new_world, new_rank):
+    """The pieces of `new_rank`'s slice of a batch that was cut over `old_world` ranks and is to be cut over `new_world` (both by
+    shard_range): a list of (old_rank, old_local_lo, new_local_lo, count) in ascending order -- `count` trajectories that start at
+    local index old_local_lo of old_rank's slice and go to local index new_local_lo of the new one.  Empty pieces are left out."""
+    lo, hi = shard_range(total, new_rank, new_world)
+    plan = []
+    for r in range(int(old_world)):
+        olo, ohi = shard_range(total, r, old_world)
+        a, b = max(lo, olo), min(hi, ohi)
+        if b > a:
+            plan.append((r, a - olo, a - lo, b - a))
+    return plan
+
+
+def regroup(old_handles, new_handles):
+    """Re-cut one batch that runs as the controllers `old_handles` (rank order, slices by shard_range) into `new_handles` (likewise)
+    by reshard_plan, on the device and inside ONE process.  A new controller that one old controller covers whole is filled by
+    transfer_state; one that is assembled from several takes their pack_state pieces as a single unpack_state, because only a call
+    that fills a whole controller lets it adopt the estimator flags of the running ones (a fresh controller's own say "no previous
+    transition").  Moving rows between processes is the caller's business -- torch.distributed send / recv of the pack_state tensor --
+    and no part of this module."""
+    import torch
+
+    total = sum(h.B for h in old_handles)
+    ow, nw = len(old_handles), len(new_handles)
+    if total != sum(h.B for h in new_handles):
+        raise ValueError("regroup: %d trajectories in, %d out" % (total, sum(h.B for h in new_handles)))
+    for hs, w in ((old_handles, ow), (new_handles, nw)):
+        for r, h in enumerate(hs):
+            lo, hi = shard_range(total, r, w)
+            if h.B != hi - lo:
+                raise ValueError("regroup: controller %d of %d holds %d trajectories, shard_range gives it %d" % (r, w, h.B, hi - lo))
+    for r, new in enumerate(new_handles):
+        plan = reshard_plan(total, ow, nw, r)
+        if len(plan) == 1:
+            orank, olo, nlo, cnt = plan[0]
+            new.transfer_state(old_handles[orank], src_idx=torch.arange(olo, olo + cnt), dst_idx=None)
+            continue
+        rows = torch.empty(new.B, new.state_row_elems(), dtype=new.dtype, device=new.device)
+        for orank, olo, nlo, cnt in plan:
+            old_handles[orank].pack_state(torch.arange(olo, olo + cnt), out=rows[nlo:nlo + cnt])
+        new.unpack_state(rows)
+
+
 def force_collectives():
     """KMPC_FORCE_COLLECTIVES=1: run the collectives of the path on a one-rank process group too (a rehearsal of the RCCL calls on a
     one-GPU box: communicator set-up, dtype, stream order -- `bench.py --force-process-group`)."""
