@@ -202,7 +202,11 @@ int kmpc_step(kmpc_handle* h, const void* X_dev, const void* ref_dev, int ref_pe
  * (Koopman_update.m:94-98), [A B] = (Ylift V')(G + I/P0)^-1, C = (X Xlift')(G_LL + I/barQ0)^-1 -- B rank-one
  * RLS updates of a shared inv_K_G (duffing.py:927-953) are exactly G <- G + sum_b z_b z_b'.  With the batch
  * sharded over GPUs the only exchange of the path is the sum of `delta_gram` over ranks between the two
- * stages (ncclAllReduce / torch.distributed.all_reduce on the caller's side; (p+L+n)*p float64 values).   */
+ * stages (ncclAllReduce / torch.distributed.all_reduce on the caller's side; (p+L+n)*p float64 values).
+ * Shapes: every y = psi handle, and y = C x with L = 64, build the condensed QP in one workgroup that keeps
+ * Gamma_0 .. Gamma_N in LDS, (L^2 + L + q L + (N+1) q L + 2 N q) * 8 bytes <= 160 KiB.  A handle past that
+ * (y = psi at L = N = 30) gets -3 from kmpc_shared_local_gram, kmpc_shared_solve[_plant] and
+ * kmpc_shared_rollout before the call allocates, launches or changes anything of the handle.            */
 int64_t kmpc_gram_elems(const kmpc_handle* h);
 /* the exchange itself for native callers: delta_gram_dev <- sum over the ranks of `nccl_comm` (an
  * ncclComm_t of the RCCL the caller loaded; ncclAllReduce, float64, sum) on `stream`.  RCCL is looked up in

@@ -1414,10 +1414,28 @@ struct Impl : kmpc_handle {
     dKs = std::move(ks); dCs = std::move(cs); dHs = std::move(hs); dFs = std::move(fs); df0s = std::move(f0s);
     return 0;
   }
+  // the route of the model stage: one launch (shared_model_kernel / shared_model2_kernel), or the round-1 pair shared_solve_kernel +
+  // shared_condense_kernel (every y = psi handle, y = C x with L + 1 > 64)
+  bool shared_one_launch() const {
+    static const bool two_kernels = dbg_env("KMPC_SHARED_TWO_KERNELS") != nullptr;  // measurement aid: the round-1 launches
+    return !two_kernels && cfg.output_kind == KMPC_OUT_CX && shared_model_available(L, n, q, N, cfg.delta_u ? 1 : 0);
+  }
+  // Every entry of the shared-model mode asks this before it allocates or launches anything: a shape the pair cannot take (the condensed
+  // QP keeps Gamma_0 .. Gamma_N, (N + 1) q L values, in the LDS of one workgroup) used to surface as the launcher's hipErrorInvalidValue
+  // after G <- lambda G + delta and the model solve had already changed the handle.
+  int shared_route_check(const char* who) {
+    const int du = cfg.delta_u ? 1 : 0;
+    if (shared_one_launch() || shared_condense_fits(L, n, q, N, du)) return 0;
+    FAIL(-3, std::string(who) + ": the condensed QP of the shared model does not fit this shape: with " +
+                 (cfg.output_kind == KMPC_OUT_LIFT ? "y = psi (q = L = " : "y = C x (q = ") + std::to_string(q) + " output rows), L = " + std::to_string(L) +
+                 ", N = " + std::to_string(N) + " shared_condense_kernel needs " + std::to_string(shared_condense_lds_bytes(L, q, N, du)) +
+                 " bytes of LDS and a workgroup has " + std::to_string(SHARED_LDS_MAX) + "; the handle is unchanged (kmpc_step takes this shape)");
+  }
   int shared_local_gram(const void* X, double* delta, hipStream_t s) override {
     if (!X || !delta) FAIL(-3, "kmpc_shared_local_gram: null pointer");
-    int rc = shared_alloc();
+    int rc = shared_route_check("kmpc_shared_local_gram");
     if (rc) return rc;
+    if ((rc = shared_alloc())) return rc;
     if (core && (rc = ensure_dense(s, true))) return rc;  // (psi, u_{k-1} and the ping-pong index are this side's from here on)
     T* psi_now = dPsi[cur];
     T* psi_prev = dPsi[cur ^ 1];
@@ -1469,8 +1487,9 @@ struct Impl : kmpc_handle {
     if (!X || !ref || steps < 0) FAIL(-3, "kmpc_shared_rollout: bad arguments");
     if (n != 2) FAIL(-3, "plants are two-state systems");
     if (!plant_id_ok(plant)) FAIL(-3, "unknown plant");
-    int rc = shared_alloc();
+    int rc = shared_route_check("kmpc_shared_rollout");
     if (rc) return rc;
+    if ((rc = shared_alloc())) return rc;
     HIPCHK(dDelta.ensure((size_t)gram_elems()));
     HIPCHK(dU0.ensure((size_t)B));
     typedef ncclResult_t (*allreduce_fn)(const void*, void*, size_t, ncclDataType_t, ncclRedOp_t, ncclComm_t, hipStream_t);
@@ -1504,14 +1523,14 @@ struct Impl : kmpc_handle {
     if (!delta || !ref || !U0) FAIL(-3, "kmpc_shared_solve: null pointer");
     if (have_wterm && wterm_from_dare && wterm_per_traj)
       FAIL(-3, "kmpc_shared_solve: per-trajectory terminal blocks do not apply to the shared model (kmpc_terminal_from_dare with per_trajectory = 0)");
-    int rc = shared_alloc();
+    int rc = shared_route_check("kmpc_shared_solve");
     if (rc) return rc;
+    if ((rc = shared_alloc())) return rc;
     if (core && (rc = ensure_dense(s, true))) return rc;
     const T* wt = !have_wterm ? nullptr : (wterm_from_dare ? (const T*)dWtB.get() : dWt.get());
     const int okind = cfg.output_kind == KMPC_OUT_LIFT ? OUT_LIFT : OUT_CX;
     const int cy0 = cfg.output_kind == KMPC_OUT_LIFT ? 0 : cfg.out_row0;
-    static const bool two_kernels = dbg_env("KMPC_SHARED_TWO_KERNELS") != nullptr;  // measurement aid: the round-1 launches
-    const bool one_launch = !two_kernels && cfg.output_kind == KMPC_OUT_CX && shared_model_available(L, n, q, N, cfg.delta_u ? 1 : 0);
+    const bool one_launch = shared_one_launch();
     if (have_prev && !one_launch) HIPCHK(launch_axpby(dGram, delta, cfg.lambda, (int)gram_elems(), s));
     if (one_launch) {
       // model solve + condensed QP + the tableau the box QPs start from, one launch (shared_model_kernel)
@@ -1550,7 +1569,7 @@ struct Impl : kmpc_handle {
     } else {
       if (have_prev) {
         HIPCHK(launch_shared_solve<T>(dGram, L, n, 1.0 / cfg.P0, 1.0 / cfg.barQ0,
-                                      cfg.output_kind == KMPC_OUT_CX ? 1 : 0, dKs, dCs, s));
+                                      cfg.output_kind == KMPC_OUT_CX ? 1 : 0, dKs, dCs, s, nullptr, nullptr, 1));
         shared_has_samples = true;
       }
       HIPCHK(launch_shared_condense<T>(dKs, dCs, (const T*)ref, L, n, q, N, okind, cfg.Qw, cfg.Rw, dHs, dFs, df0s, s, wt,

@@ -297,7 +297,7 @@ template <typename S, typename D> hipError_t launch_cast(const S* src, D* dst, s
 template <typename T> hipError_t launch_gram(const GramArgs<T>& a, double forget, double* gram, hipStream_t s);
 template <typename T> hipError_t launch_shared_solve(const double* gram, int L, int n, double dP, double dQ, int use_C,
                                                      T* Kout, T* Cout, hipStream_t s, T* Pout = nullptr,
-                                                     T* Qout = nullptr);
+                                                     T* Qout = nullptr, int refine = 0);
 template <typename T> hipError_t launch_shared_condense(const T* K, const T* C, const T* ref, int L, int n, int q, int N,
                                                         int out_kind, double Qw, double Rw, T* Hout, T* Fout, T* f0out,
                                                         hipStream_t s, const T* Wterm = nullptr, int du_mode = 0,
@@ -313,6 +313,21 @@ hipError_t launch_shared_model(double* gram, const double* delta, double forget,
 template <typename T>
 hipError_t launch_shared_fast(const StepArgs<T>& a, int32_t* need, hipStream_t s);
 bool shared_model_available(int Lm, int n, int q, int N, int du_mode);
+// the two-kernel route (shared_solve_kernel + shared_condense_kernel: every y = psi handle, y = C x past shared_model_available): the LDS its
+// two launches ask for -- the launchers and the up-front check of api.hip (Impl::shared_route_check) read the same two formulas
+constexpr size_t SHARED_LDS_MAX = 160 * 1024;
+// (refine: shared_solve_kernel with its step of iterative refinement also keeps G and the unrefined [A B])
+inline size_t shared_solve_lds_bytes(int L, int n, int refine) {
+  const size_t p = (size_t)L + 1;
+  return (p * (p + 1) + (size_t)(L + n) * p + (refine ? p * p + (size_t)L * p : 0)) * sizeof(double);
+}
+inline size_t shared_condense_lds_bytes(int Lm, int q, int N, int du_mode) {
+  const size_t L = (size_t)Lm + (du_mode ? 1 : 0);
+  return (L * L + L + (size_t)q * L + (size_t)(N + 1) * q * L + 2 * (size_t)N * q) * sizeof(double);
+}
+inline bool shared_condense_fits(int Lm, int n, int q, int N, int du_mode) {
+  return shared_solve_lds_bytes(Lm, n, 1) <= SHARED_LDS_MAX && shared_condense_lds_bytes(Lm, q, N, du_mode) <= SHARED_LDS_MAX;
+}
 // shared_model2_kernel (round 4): shared_model_kernel on sixteen waves (float64, q <= 2, N >= 12, L~ <= 33)
 struct SharedModel2Args {
   double* gram; const double* delta; double forget; const double* ref;
