@@ -11,6 +11,7 @@
 #include "../../include/koopmpc.h"
 #include "devbuf.h"
 #include "kernels.h"
+#include "state_home.h"
 #include "state_rows.h"
 #include <dlfcn.h>
 #include <rccl/rccl.h>  // types and enumerators only (ncclDouble, ncclSum): the library resolves ncclAllReduce at run time
@@ -229,29 +230,98 @@ static inline int64_t blob_bytes(const Sections& t) { return (int64_t)sizeof(Blo
 template <typename T>
 struct Impl : kmpc_handle {
   int n, m, L, p, q, N, B, threads;
-  EncoderShape enc{};  // the encoder as the kernels see it (effective hidden width, padding, k-steps)
-  int Lenc = 0;        // the encoder's own output dimension (lift_offset)
-  std::vector<std::vector<double>> hostW, hostb;  // the layers as given (row-major), kept for finalize_encoder
   long sP, sK, sQ, sC;
-  // persistent state
+  // ---- persistent state
   // (every device block of the handle is a DevBuf, csrc/devbuf.h: freed with the handle, no list to keep)
   DevBuf<T> dP, dK, dQ, dC;
   DevBuf<T> dPsi[2];  // [B][L] trajectory-major: [cur], [prev]
   DevBuf<T> dUprev;
+  DevBuf<T> dWarm;  // [N][B] last minimiser = start of the next solve (the reference restarts at zeros, duffing.py:634-635)
   DevBuf<T> dQpScr;  // [batch][N*N] fall-back tableau of the register QP solvers (global scratch, rarely touched); grown by kmpc_qp_solve
+  // four-wave solver (threads = 256, float64): every trajectory's last tableau and its variable set, kept from step to step
+  // (StepArgs::qp_carry); any change of the model from outside forgets them (the next solve starts from 2H)
+  DevBuf<T> dQpCarry;
+  DevBuf<int32_t> dQpCarrySet;
   // Register-state step (step_v2.h): the fused roll-out of the small y = C x dimension sets streams the state as a "wave image"
-  // ([B][sImg] doubles).  The dense blocks above stay the form every other entry point works on; whichever of the two was
-  // written last is the valid one and the other is rebuilt on demand (state_to_image / image_to_state, one pass over the state).
+  // ([B][sImg] doubles).  The dense blocks above stay the form every other entry point works on; the image is the fast form of
+  // `home` (csrc/state_home.h: which of the two is valid, and when the other is rebuilt by state_to_image / image_to_state, one
+  // pass over the state).
   DevBuf<double> dImg;
   long sImg = 0;
-  bool use_img = false, img_valid = false, dense_valid = true;
+  bool use_img = false;
   // KMPC_F32 handle of a register-state dimension set (row g2: BASELINE configs[1] names fp32; SURVEY G6: fp32 panels, float64
   // covariance): kmpc_rollout runs the float64 fused roll-out behind float32 panels.  `core` is a float64 handle of the same
   // configuration that owns the state while roll-outs run (its wave image; psi_{k-1}, u_{k-1}, the warm start in float64); the
-  // float32 blocks of this handle are the form every other entry point works on.  Whichever side was written last is the valid one
-  // (dense_valid / img_valid as for the wave image) and the other is rebuilt on demand by a cast over the blocks (core_push / core_pull).
+  // float32 blocks of this handle are the form every other entry point works on.  The core is the fast form of this handle's
+  // `home` (csrc/state_home.h); the other side is rebuilt on demand by a cast over the blocks (core_push / core_pull).
   Impl<double>* core = nullptr;
   bool is_core = false;  // this handle IS the float64 core of a float32 handle
+  StateHome home;        // where the per-trajectory state is valid: ensure_dense / ensure_image
+  Progress prog;         // psi_k's buffer; a previous (psi, u) exists -> next step runs the RLS update; that update starts from K_A = 0, bar_X = 0
+  // the loop WITHOUT the online update (duffing.py:738-805, vanderpol.py:645-722): kmpc_step / kmpc_rollout skip the RLS phase and
+  // solve with the model as it is; the lift / input history keeps running, so that switching the update back on continues
+  bool update_on = true;
+  DevBuf<T> dMsK, dMsC, dMsH, dMsf, dMsc, dMsW;  // kmpc_mpc_solve: scratch model blocks, H, f, c, terminal block
+  // ---- parameters
+  EncoderShape enc{};  // the encoder as the kernels see it (effective hidden width, padding, k-steps)
+  int Lenc = 0;        // the encoder's own output dimension (lift_offset)
+  std::vector<std::vector<double>> hostW, hostb;  // the layers as given (row-major), kept for finalize_encoder
+  DevBuf<T> dW1, db1, dWh[2], dbh[2], dWo, dbo, dcx, dTmp;
+  DevBuf<T> dWhp[2], dWop;  // hidden / output weights as MFMA A-fragments
+  bool packed_ok = false;
+  std::vector<bool> layer_set;
+  bool centres_set = false;
+  int rbf_k = 1;  // polyharmonic coefficient (rbf.m:15-17), kmpc_set_rbf_order
+  // ---- fused roll-out (one launch for all the steps; rollout_kernel in step_kernel.hip)
+  DevBuf<T> dU0;  // rollout scratch [B]
+  DevBuf<int32_t> dWork;  // [B] solver work of every trajectory in the last fused launch (RolloutArgs::work)
+  DevBuf<int32_t> dPerm;  // [B] slot -> trajectory for the next fused launch (RolloutArgs::perm); valid after a launch that wrote dWork
+  bool place_valid = false;
+  hipEvent_t evPlace = nullptr;      // recorded behind the launch (and the rank pass) that wrote dWork / dPerm
+  hipStream_t place_stream = nullptr;
+  // kmpc_set_rollout_diagnostics / kmpc_rollout_diag: the reference's logXLOClift and A_error, B_error, C_error (duffing.py:850, 985-990,
+  // 1015) from inside the roll-out.  Fused route: rollout_kernel<.., DIAG> (a plug-in made by the setter, also for the built-in sets;
+  // with a terminal refresh armed the variant that has both); every other route: rls_diag_kernel in front of each step's update.
+  bool diag_on = false;
+  // ---- shared-model mode
+  DevBuf<double> dGram, dPartial;  // (dGram set: the handle has its shared-model blocks, all seven -- shared_alloc)
+  DevBuf<T> dKs, dCs, dHs, dFs, df0s, dTs;
+  DevBuf<double> dFastPack;      // F, T0, H of the shared model as shared_fast_kernel's operand fragments (SharedModel2Args::pack)
+  bool fast_pack_valid = false;  // ... written by the last model launch
+  DevBuf<int32_t> dNeed;  // [B] flags of shared_fast_kernel
+  DevBuf<int32_t> dQpList;  // two alternating counters, then the list of the trajectories shared_fast_kernel left to the solve-only kernel
+  int qp_list_parity = 0;
+  DevBuf<double> dDelta;  // kmpc_shared_rollout: this rank's Gram sums of a step (all-reduced in place)
+  bool shared_has_samples = false;
+  static constexpr int GRAM_BLOCKS = 256;  // partial blocks of the Gram kernels (512 measured slower: lift + Gram 21.8 vs 17.2 us, reduce 7.6 vs 4.8 us)
+  // ---- terminal block (PN - Qw I of Q_bar; the kinds: Term, csrc/state_home.h)
+  Term wterm = Term::None;
+  DevBuf<T> dWt;  // the block given to kmpc_set_terminal_weight
+  std::vector<double> hostPN;  // P_N as given to kmpc_set_terminal_weight
+  // kmpc_terminal_from_dare: Riccati workspace and the block(s) it produced ([1] or [B][q*q], PN - Qw I)
+  DevBuf<double> dDareP, dWtB;
+  DevBuf<int32_t> dDareIt;
+  int dare_cap = 0;  // models the three hold room for (dare_buffers alone changes it)
+  DevBuf<double> dEyeL;  // L x L identity: the output map of y = psi
+  // kmpc_set_terminal_refresh: the MATLAB controller recomputes its terminal ingredients with the updated model at EVERY iteration
+  // (Koopman_update.m:215 dlqr, :381 Q_bar(end) = C P C').  every > 0: kmpc_step / kmpc_rollout run the reference's Riccati iteration
+  // (duffing.py:583-598) on every trajectory's freshly updated [A B] each `every`-th step and rebuild its block Co P Co' before the
+  // condensed QP is formed -- INSIDE the launch for the fused roll-out (rollout_kernel<.., TERM>, a plug-in made here), as RLS launch /
+  // dare_kernel / QP launch on the per-step route.  0: off (the blocks stay what the last refresh left).
+  int term_every = 0, term_maxiter = 500;
+  long term_count = 0;
+  double term_R = 0.01, term_eps = 0.01;
+  DevBuf<double> dTermQ, dTermScr;
+  // ---- packed rows
+  DevBuf<int32_t> dRowChk;  // [B] marks of the duplicate check, then the status word of state_rows_check_kernel
+  DevBuf<T> dRowStage;      // kmpc_state_transfer into this handle: the packed rows between gather and scatter, grown on demand
+  // ---- profiling
+  bool prof = false;
+  std::vector<hipEvent_t> ev;  // triples
+  size_t ev_used = 0;
+  static constexpr size_t EV_CAP = 3 * 4096;
+  int64_t prof_steps = 0;  // control steps covered by the recorded events
+
   // The fused roll-out objects of this handle's dimension set (rollout_plugin.hip), variant[term][diag]: [0][0] the plain kernel (loaded by
   // init unless the set is built-in), [1][0] with the terminal refresh inside (kmpc_set_terminal_refresh), [.][1] with the diagnostics logs
   // (kmpc_set_rollout_diagnostics).  state: 0 not asked for / built-in set / no fused roll-out at all, 1 loaded, -1 could not be made or no
@@ -281,29 +351,11 @@ struct Impl : kmpc_handle {
   //  with y = C x and as many output rows as lifted states (n = 2, L = 2, both rows of C) would track psi(x).  It keeps the per-step
   //  launches, whose launcher hands such a handle to the generic kernel: step_kernel.hip launch_step)
   bool fused_kind_ok() const { return (q == L) == (cfg.output_kind == KMPC_OUT_LIFT); }
-  // four-wave solver (threads = 256, float64): every trajectory's last tableau and its variable set, kept from step to step
-  // (StepArgs::qp_carry); any change of the model from outside forgets them (the next solve starts from 2H)
-  DevBuf<T> dQpCarry;
-  DevBuf<int32_t> dQpCarrySet;
-  DevBuf<T> dWarm;  // [N][B] last minimiser = start of the next solve (the reference restarts at zeros, duffing.py:634-635)
-  int cur = 0;
-  bool have_prev = false;  // a previous (psi, u) exists -> next step runs the RLS update
-  bool rls_fresh = true;   // next RLS update starts from K_A = 0, bar_X = 0
-  // parameters
-  DevBuf<T> dW1, db1, dWh[2], dbh[2], dWo, dbo, dcx, dTmp;
-  std::vector<bool> layer_set;
-  bool centres_set = false;
-  int rbf_k = 1;  // polyharmonic coefficient (rbf.m:15-17), kmpc_set_rbf_order
   // what the lift kernels get in LiftArgs / RolloutArgs::rbf_matlab: 0 / 1 the thin plates, else the kind with k in bits 8-15 (plant_device.h)
   int rbf_code() const {
     if (cfg.lift_kind <= KMPC_LIFT_RBF_MATLAB) return cfg.lift_kind == KMPC_LIFT_RBF_MATLAB ? 1 : 0;
     return cfg.lift_kind | (rbf_k << 8);
   }
-  // profiling
-  bool prof = false;
-  std::vector<hipEvent_t> ev;  // triples
-  size_t ev_used = 0;
-  static constexpr size_t EV_CAP = 3 * 4096;
 
   int init(const kmpc_config& c) {
     cfg = c;
@@ -340,7 +392,7 @@ struct Impl : kmpc_handle {
     // every block a checkpoint carries starts as zeros, the padding of the strides included (reset() below fills P and bar_Q)
     const Sections blocks = sections(blob_header());
     for (int i = 0; i < blocks.n_traj; ++i) HIPCHK(hipMemset(blocks.s[i].ptr, 0, blocks.s[i].bytes()));
-    HIPCHK(hipMemset(dPsi[cur], 0, sizeof(T) * (size_t)L * B));
+    HIPCHK(hipMemset(dPsi[prog.cur], 0, sizeof(T) * (size_t)L * B));
     if (sizeof(T) == 8 && threads == 256 && !dbg_env("KMPC_QP_NO_CARRY")) {  // (the variable is a measurement aid)
       HIPCHK(dQpCarry.alloc((size_t)B * N * N));
       HIPCHK(dQpCarrySet.alloc((size_t)B * 4));
@@ -360,6 +412,7 @@ struct Impl : kmpc_handle {
         sImg = state_image_elems(L, n);
         HIPCHK(dImg.alloc((size_t)sImg * B));
       }
+      home.has_fast = use_img;
     }
     if constexpr (sizeof(T) == 4) {
       if (fused_dims_ok() && io32_ok) {
@@ -370,6 +423,7 @@ struct Impl : kmpc_handle {
         const int rc = core->init(c64);
         if (rc) { err = "float64 core of the float32 handle: " + core->err; delete core; core = nullptr; return rc; }
         core->variant[0][0].plugin = variant[0][0].plugin;
+        home.has_fast = true;
       }
     }
     if (c.lift_kind == KMPC_LIFT_MLP) {
@@ -426,70 +480,68 @@ struct Impl : kmpc_handle {
 
   // the dense blocks are about to be read or modified / the wave image is about to be used by the roll-out
   int ensure_dense(hipStream_t s, bool will_modify) {
-    if constexpr (sizeof(T) == 8) {
-      if (use_img && !dense_valid) {
+    if (home.dense_stale()) {
+      if constexpr (sizeof(T) == 8) {
         HIPCHK(launch_image_to_state(dImg, sImg, n, L, B, (double*)dP, sP, (double*)dK, sK, (double*)dQ, sQ, (double*)dC, sC, s));
-        dense_valid = true;
-      }
-    } else {
-      if (core && !dense_valid) {
+      } else {
         const int rc = core_pull(s);
         if (rc) return rc;
-        dense_valid = true;
       }
     }
-    if (will_modify) img_valid = false;
+    home.dense_ready(will_modify);
     return 0;
   }
-  // float32 handle <-> its float64 core: the state blocks (same strides on both sides), psi_{k-1}, u_{k-1}, the warm start, the flags
+  // a call that the float64 core of a float32 handle takes too: its return code, with its message; 0 without a core
+  template <typename F>
+  int on_core(F&& f) {
+    if (!core) return 0;
+    const int rc = f(*core);
+    if (rc) err = core->err;
+    return rc;
+  }
+  // float32 handle <-> its float64 core: the state blocks (same strides on both sides), psi_{k-1}, u_{k-1}, the warm start, the progress
   int core_push(hipStream_t s) {
     if constexpr (sizeof(T) == 4) {
-      int rc = core->ensure_dense(s, true);
-      if (rc) { err = core->err; return rc; }
-      core->cur = cur;  // (both sides' tables name the same psi_{k-1} buffer)
+      const int rc = on_core([&](Impl<double>& c) { return c.ensure_dense(s, true); });
+      if (rc) return rc;
+      core->prog = prog;  // (both sides' tables name the same psi_{k-1} buffer)
       const Sections mine = sections(blob_header()), cores = core->sections(core->blob_header());
       for (int i = 0; i < mine.n_traj; ++i)
         HIPCHK((launch_cast<float, double>((const float*)mine.s[i].ptr, (double*)cores.s[i].ptr, mine.s[i].count, s)));
       // (psi_k's buffer is no part of a checkpoint, but it has always travelled with the rest)
-      HIPCHK((launch_cast<float, double>((const float*)dPsi[cur], core->dPsi[cur], (size_t)L * B, s)));
-      core->have_prev = have_prev; core->rls_fresh = rls_fresh; core->update_on = update_on;
-      core->cfg.P0 = cfg.P0; core->cfg.barQ0 = cfg.barQ0;
-      core->dense_valid = true; core->img_valid = false;
+      HIPCHK((launch_cast<float, double>((const float*)dPsi[prog.cur], core->dPsi[prog.cur], (size_t)L * B, s)));
+      core->update_on = update_on; core->cfg.P0 = cfg.P0; core->cfg.barQ0 = cfg.barQ0;
+      core->home.dense_overwritten();
     }
     return 0;
   }
   int core_pull(hipStream_t s) {
     if constexpr (sizeof(T) == 4) {
-      int rc = core->ensure_dense(s, false);
-      if (rc) { err = core->err; return rc; }
-      cur = core->cur;
+      const int rc = on_core([&](Impl<double>& c) { return c.ensure_dense(s, false); });
+      if (rc) return rc;
+      prog = core->prog;
       const Sections mine = sections(blob_header()), cores = core->sections(core->blob_header());
       for (int i = 0; i < mine.n_traj; ++i)
         HIPCHK((launch_cast<double, float>((const double*)cores.s[i].ptr, (float*)mine.s[i].ptr, mine.s[i].count, s)));
-      HIPCHK((launch_cast<double, float>(core->dPsi[cur], (float*)dPsi[cur], (size_t)L * B, s)));
-      have_prev = core->have_prev; rls_fresh = core->rls_fresh;
+      HIPCHK((launch_cast<double, float>(core->dPsi[prog.cur], (float*)dPsi[prog.cur], (size_t)L * B, s)));
     }
     return 0;
   }
-  // (called where the model or the state is replaced from outside: set_model, reset, offline fit, checkpoint import)
+  // the fast form (wave image / float64 core) is about to be advanced by the roll-out; nothing to do on a handle without one
   int ensure_image(hipStream_t s) {
-    if constexpr (sizeof(T) == 8) {
-      if (!img_valid) {
+    if (home.fast_stale()) {
+      if constexpr (sizeof(T) == 8) {
         HIPCHK(launch_state_to_image((const double*)dP, sP, (const double*)dK, sK, (const double*)dQ, sQ, (const double*)dC, sC, n, L, B, dImg, sImg, s));
-        img_valid = true;
-      }
-      dense_valid = false;  // (the roll-out writes the image)
-    } else if (core) {
-      if (!img_valid) {
+      } else {
         const int rc = core_push(s);
         if (rc) return rc;
-        img_valid = true;
       }
-      dense_valid = false;  // (the roll-out advances the core's state)
     }
+    home.fast_taken();
     return 0;
   }
 
+  // (called where the model or the state is replaced from outside: set_model, reset, offline fit, checkpoint import)
   int forget_tableaux(hipStream_t s) {
     if (dQpCarrySet) HIPCHK(hipMemsetAsync(dQpCarrySet, 0, sizeof(int32_t) * (size_t)B * 4, s));
     return 0;
@@ -506,7 +558,7 @@ struct Impl : kmpc_handle {
     hostb[layer].assign(b, b + rows);
     layer_set[layer] = true;
     packed_ok = false;
-    if (core) { const int rc = core->set_encoder_layer(layer, W, b, rows, cols); if (rc) { err = core->err; return rc; } }
+    if (const int rc = on_core([&](Impl<double>& c) { return c.set_encoder_layer(layer, W, b, rows, cols); })) return rc;
     for (int k = 0; k < nl; ++k)
       if (!layer_set[k]) return 0;
     return finalize_encoder();
@@ -570,7 +622,7 @@ struct Impl : kmpc_handle {
     if (L_ != L || n_ != n) FAIL(-3, "centre shape does not match the configuration");
     int rc = upload_padded(dcx, cx, L, n, L, n);
     if (rc) return rc;
-    if (core && (rc = core->set_centres(cx, L_, n_))) { err = core->err; return rc; }
+    if ((rc = on_core([&](Impl<double>& c) { return c.set_centres(cx, L_, n_); }))) return rc;
     centres_set = true;
     return 0;
   }
@@ -578,7 +630,7 @@ struct Impl : kmpc_handle {
   int set_rbf_order(int k) override {
     if (cfg.lift_kind != KMPC_LIFT_RBF_POLYHARMONIC) FAIL(-3, "handle was not created with KMPC_LIFT_RBF_POLYHARMONIC");
     if (k < 1 || k > 8) FAIL(-3, "the polyharmonic coefficient k must be an integer in 1..8");
-    if (core) { const int rc = core->set_rbf_order(k); if (rc) { err = core->err; return rc; } }
+    if (const int rc = on_core([&](Impl<double>& c) { return c.set_rbf_order(k); })) return rc;
     rbf_k = k;
     return 0;
   }
@@ -614,28 +666,42 @@ struct Impl : kmpc_handle {
   // (a float32 handle's float64 core gets the block this handle itself works with -- PN - Qw I rounded to float32 -- so that the
   //  fused roll-outs, the per-step entry points and a checkpoint loaded into another handle all use the same weight: core_weight)
   int core_weight(const std::vector<T>* w) {
-    if (!core) return 0;
     std::vector<double> pn;
-    if (w) {
-      pn.resize(w->size());
-      for (int r = 0; r < q; ++r)
-        for (int c2 = 0; c2 < q; ++c2) pn[(size_t)r * q + c2] = (double)(*w)[(size_t)r * q + c2] + (r == c2 ? cfg.Qw : 0.0);
-    }
-    const int rc = core->set_terminal_weight(w ? pn.data() : nullptr);
-    if (rc) err = core->err;
-    return rc;
+    if (w) pn = pn_from_block(*w, cfg.Qw);
+    return on_core([&](Impl<double>& c) { return c.set_terminal_weight(w ? pn.data() : nullptr); });
   }
-  int set_terminal_weight(const double* PN) override {
-    wterm_from_dare = false;
-    if (!PN) { have_wterm = false; hostPN.clear(); return core_weight(nullptr); }
+  // the block the kernels add to Q_bar's last diagonal block, P_N - Qw I in the handle's dtype, and P_N back from it
+  std::vector<T> block_from_pn(const double* PN, double Qw) const {
     std::vector<T> w((size_t)q * q);
     for (int r = 0; r < q; ++r)
-      for (int c2 = 0; c2 < q; ++c2) w[(size_t)r * q + c2] = (T)(PN[(size_t)r * q + c2] - (r == c2 ? cfg.Qw : 0.0));
+      for (int c2 = 0; c2 < q; ++c2) w[(size_t)r * q + c2] = (T)(PN[(size_t)r * q + c2] - (r == c2 ? Qw : 0.0));
+    return w;
+  }
+  std::vector<double> pn_from_block(const std::vector<T>& w, double Qw) const {
+    std::vector<double> pn(w.size());
+    for (int r = 0; r < q; ++r)
+      for (int c2 = 0; c2 < q; ++c2) pn[(size_t)r * q + c2] = (double)w[(size_t)r * q + c2] + (r == c2 ? Qw : 0.0);
+    return pn;
+  }
+  // the handle's terminal block(s) as the kernels read them; null: none
+  T* wterm_ptr() const { return wterm == Term::None ? nullptr : (term_from_dare(wterm) ? (T*)dWtB.get() : dWt.get()); }
+  int32_t wterm_block_count(Term t) const { return t == Term::None ? 0 : (t == Term::DarePerTraj ? B : 1); }
+  // every trajectory gets the one block w0 ([q q]) as its own Riccati block: dWtB becomes [B][q q]
+  int spread_block(const std::vector<double>& w0) {
+    { int rc = dare_buffers(B); if (rc) return rc; }
+    std::vector<double> wb((size_t)B * q * q);
+    for (int b = 0; b < B; ++b) std::copy(w0.begin(), w0.end(), wb.begin() + (size_t)b * q * q);
+    HIPCHK(hipMemcpy(dWtB, wb.data(), sizeof(double) * wb.size(), hipMemcpyHostToDevice));
+    return 0;
+  }
+  int set_terminal_weight(const double* PN) override {
+    if (!PN) { wterm = Term::None; hostPN.clear(); return core_weight(nullptr); }
+    const std::vector<T> w = block_from_pn(PN, cfg.Qw);
     { const int rc = core_weight(&w); if (rc) return rc; }
     HIPCHK(dWt.ensure((size_t)q * q));
     HIPCHK(hipMemcpy(dWt, w.data(), w.size() * sizeof(T), hipMemcpyHostToDevice));
     hostPN.assign(PN, PN + (size_t)q * q);
-    have_wterm = true;
+    wterm = Term::Given;
     return 0;
   }
 
@@ -668,9 +734,7 @@ struct Impl : kmpc_handle {
         if (iters_out) HIPCHK(hipMemcpy(iters_out, dDareIt, sizeof(int32_t) * (size_t)nb, hipMemcpyDeviceToHost));
       }
       HIPCHK(hipStreamSynchronize(s));
-      wterm_per_traj = per_traj != 0;
-      wterm_from_dare = true;
-      have_wterm = true;
+      wterm = per_traj ? Term::DarePerTraj : Term::DareOne;
       return 0;
     }
   }
@@ -683,7 +747,6 @@ struct Impl : kmpc_handle {
     dare_cap = nb;
     return 0;
   }
-  DevBuf<double> dEyeL;  // L x L identity: the output map of y = psi
   // P = DARE(A, B, Qdev, R) of the first nb trajectories' current [A B] and their blocks Co P Co' - Qw I -> dWtB   (dare_kernel)
   int dare_blocks(int nb, const double* Qdev, double R, int maxiter, double eps, hipStream_t s) {
     if constexpr (sizeof(T) == 8) {
@@ -708,15 +771,7 @@ struct Impl : kmpc_handle {
     return 0;
   }
 
-  // kmpc_set_terminal_refresh: the MATLAB controller recomputes its terminal ingredients with the updated model at EVERY iteration
-  // (Koopman_update.m:215 dlqr, :381 Q_bar(end) = C P C').  every > 0: kmpc_step / kmpc_rollout run the reference's Riccati iteration
-  // (duffing.py:583-598) on every trajectory's freshly updated [A B] each `every`-th step and rebuild its block Co P Co' before the
-  // condensed QP is formed -- INSIDE the launch for the fused roll-out (rollout_kernel<.., TERM>, a plug-in made here), as RLS launch /
-  // dare_kernel / QP launch on the per-step route.  0: off (the blocks stay what the last refresh left).
-  int term_every = 0, term_maxiter = 500;
-  long term_count = 0;
-  double term_R = 0.01, term_eps = 0.01;
-  DevBuf<double> dTermQ, dTermScr;
+  // kmpc_set_terminal_refresh (what it does: the comment at term_every)
   int set_terminal_refresh(int every, const double* Qh, double R, int maxiter, double eps) override {
     if constexpr (sizeof(T) != 8) {
       FAIL(-2, "kmpc_set_terminal_refresh: float64 handles only (the reference's Riccati iteration is float64)");
@@ -728,22 +783,13 @@ struct Impl : kmpc_handle {
         return 0;
       }
       { int rc = sync_own(); if (rc) return rc; }
-      const bool had = have_wterm, had_per_traj = have_wterm && wterm_from_dare && wterm_per_traj;
-      const int old_cap = dare_cap;
       std::vector<double> w0((size_t)q * q, 0.0);  // the block every trajectory holds until its first refresh: the current one, else Qw I
-      if (had && !had_per_traj) {
-        if (wterm_from_dare) HIPCHK(hipMemcpy(w0.data(), dWtB, sizeof(double) * w0.size(), hipMemcpyDeviceToHost));
-        else HIPCHK(hipMemcpy(w0.data(), dWt, sizeof(double) * w0.size(), hipMemcpyDeviceToHost));
-      }
-      if (!(had_per_traj && old_cap >= B)) {
-        { int rc = dare_buffers(B); if (rc) return rc; }
-        std::vector<double> wb((size_t)B * q * q);
-        for (int b = 0; b < B; ++b) std::copy(w0.begin(), w0.end(), wb.begin() + (size_t)b * q * q);
-        HIPCHK(hipMemcpy(dWtB, wb.data(), sizeof(double) * wb.size(), hipMemcpyHostToDevice));
-      }
+      if (wterm == Term::Given || wterm == Term::DareOne)
+        HIPCHK(hipMemcpy(w0.data(), wterm_ptr(), sizeof(double) * w0.size(), hipMemcpyDeviceToHost));
+      if (!(wterm == Term::DarePerTraj && dare_cap >= B)) { int rc = spread_block(w0); if (rc) return rc; }
       HIPCHK(dTermQ.ensure((size_t)L * L));
       HIPCHK(hipMemcpy(dTermQ, Qh, sizeof(double) * (size_t)L * L, hipMemcpyHostToDevice));
-      have_wterm = true; wterm_from_dare = true; wterm_per_traj = true;
+      wterm = Term::DarePerTraj;
       term_R = R; term_maxiter = maxiter; term_eps = eps; term_count = 0;
       // the fused roll-out of this configuration with the refresh inside: a plug-in of its own (also for the built-in dimension sets)
       variant[1][0].state = 0;
@@ -755,10 +801,6 @@ struct Impl : kmpc_handle {
     }
   }
 
-  // kmpc_set_rollout_diagnostics / kmpc_rollout_diag: the reference's logXLOClift and A_error, B_error, C_error (duffing.py:850, 985-990,
-  // 1015) from inside the roll-out.  Fused route: rollout_kernel<.., DIAG> (a plug-in made by the setter, also for the built-in sets;
-  // with a terminal refresh armed the variant that has both); every other route: rls_diag_kernel in front of each step's update.
-  bool diag_on = false;
   // the DIAG variant this handle needs now (asked for once); 0: the fused route is ready, 1: per-step launches
   int load_diag_plugins() {
     if constexpr (sizeof(T) == 8) {
@@ -777,12 +819,12 @@ struct Impl : kmpc_handle {
   int estimator_status(double* P0o, double* barQ0o) const override {
     if (P0o) *P0o = cfg.P0;
     if (barQ0o) *barQ0o = cfg.barQ0;
-    return (have_prev ? 1 : 0) | ((rls_fresh && update_on) ? 2 : 0);
+    return (prog.have_prev ? 1 : 0) | ((prog.rls_fresh && update_on) ? 2 : 0);
   }
   // kmpc_get_prev_transition: copies of psi(x_{k-1}) ([B][L]) and u_{k-1} ([B]) the next update will regress on (stream-ordered, read-only)
   int get_prev_transition(void* psi_prev, void* u_prev, hipStream_t s) override {
     if (core) FAIL(-2, "kmpc_get_prev_transition: float64 handles only");
-    if (psi_prev) HIPCHK(hipMemcpyAsync(psi_prev, dPsi[cur ^ 1], sizeof(T) * (size_t)L * B, hipMemcpyDeviceToDevice, s));
+    if (psi_prev) HIPCHK(hipMemcpyAsync(psi_prev, dPsi[prog.cur ^ 1], sizeof(T) * (size_t)L * B, hipMemcpyDeviceToDevice, s));
     if (u_prev) HIPCHK(hipMemcpyAsync(u_prev, dUprev, sizeof(T) * (size_t)B, hipMemcpyDeviceToDevice, s));
     return 0;
   }
@@ -816,13 +858,13 @@ struct Impl : kmpc_handle {
     if constexpr (sizeof(T) == 8) {
       int rc = ensure_dense(s, true);
       if (rc) return rc;
-      if ((rc = lift_to((const T*)X, dPsi[cur], 1, L, B, s))) return rc;
+      if ((rc = lift_to((const T*)X, dPsi[prog.cur], 1, L, B, s))) return rc;
       RlsDiagArgs d{};
       d.B = B; d.n = n; d.L = L;
-      d.has_update = (have_prev && update_on) ? 1 : 0; d.first_update = rls_fresh ? 1 : 0; d.use_C = cfg.output_kind == KMPC_OUT_CX ? 1 : 0;
+      d.has_update = (prog.have_prev && update_on) ? 1 : 0; d.first_update = prog.rls_fresh ? 1 : 0; d.use_C = cfg.output_kind == KMPC_OUT_CX ? 1 : 0;
       d.P = (const double*)dP; d.strideP = sP; d.K = (const double*)dK; d.strideK = sK; d.Qb = (const double*)dQ; d.strideQ = sQ;
       d.C = (const double*)dC; d.strideC = sC;
-      d.psi_prev = (const double*)dPsi[cur ^ 1]; d.psi_now = (const double*)dPsi[cur]; d.u_prev = (const double*)dUprev; d.x_now = (const double*)X;
+      d.psi_prev = (const double*)dPsi[prog.cur ^ 1]; d.psi_now = (const double*)dPsi[prog.cur]; d.u_prev = (const double*)dUprev; d.x_now = (const double*)X;
       d.Psi_row = lg.Psi ? (double*)lg.Psi + (size_t)i * L * B : nullptr;
       d.dA_row = lg.dA ? (double*)lg.dA + (size_t)i * B : nullptr;
       d.dB_row = lg.dB ? (double*)lg.dB + (size_t)i * B : nullptr;
@@ -839,9 +881,7 @@ struct Impl : kmpc_handle {
     { int rc = forget_tableaux(s); if (rc) return rc; }
     HIPCHK(launch_fill_state<T>(dP, sP, p, (T)cfg.P0, dQ, sQ, L, (T)cfg.barQ0, nullptr, sK, nullptr, sC, n, B, s));
     HIPCHK(hipMemsetAsync(dWarm, 0, sizeof(T) * (size_t)N * B, s));  // first solve starts at clip(0) like the reference's (duffing.py:634-635)
-    have_prev = false;
-    rls_fresh = true;
-    cur = 0;
+    prog = Progress{};
     return 0;
   }
 
@@ -888,7 +928,7 @@ struct Impl : kmpc_handle {
     if (dKs) HIPCHK(hipMemcpyAsync(dKs, tK, sizeof(T) * (size_t)L * p, hipMemcpyDeviceToDevice, s));
     if (dCs) HIPCHK(hipMemcpyAsync(dCs, tC, sizeof(T) * (size_t)n * L, hipMemcpyDeviceToDevice, s));
     HIPCHK(hipStreamSynchronize(s));
-    rls_fresh = false;  // the first online update continues from these accumulators
+    prog.rls_fresh = false;  // the first online update continues from these accumulators
     return 0;
   }
 
@@ -902,6 +942,15 @@ struct Impl : kmpc_handle {
     return 0;
   }
 
+  // the MLP encoder's fields of a lift launch: the layers and (packed now if need be) their MFMA fragments
+  int encoder_args(LiftArgs<T>& a, hipStream_t s) {
+    a.W1 = dW1; a.b1 = db1; a.Wh[0] = dWh[0]; a.Wh[1] = dWh[1]; a.bh[0] = dbh[0]; a.bh[1] = dbh[1];
+    a.Wo = dWo; a.bo = dbo; a.Hp = enc.Hp; a.Lp = enc.Lp;
+    const int rc = pack_encoder(s);
+    if (rc) return rc;
+    a.Whp[0] = dWhp[0]; a.Whp[1] = dWhp[1] ? dWhp[1] : dWhp[0]; a.Wop = dWop; a.KSp = enc.KS;
+    return 0;
+  }
   int lift_to(const T* X, T* Psi, long ps_l, long ps_b, int Bc, hipStream_t s) {
     int rc = check_lift_ready();
     if (rc) return rc;
@@ -909,10 +958,7 @@ struct Impl : kmpc_handle {
     a.B = Bc; a.n = n; a.L = L; a.hidden = enc.hid; a.nlayers = cfg.layers;
     a.X = X; a.Psi = Psi; a.ps_l = ps_l; a.ps_b = ps_b;
     if (cfg.lift_kind == KMPC_LIFT_MLP) {
-      a.W1 = dW1; a.b1 = db1; a.Wh[0] = dWh[0]; a.Wh[1] = dWh[1]; a.bh[0] = dbh[0]; a.bh[1] = dbh[1];
-      a.Wo = dWo; a.bo = dbo; a.Hp = enc.Hp; a.Lp = enc.Lp;
-      if ((rc = pack_encoder(s))) return rc;
-      a.Whp[0] = dWhp[0]; a.Whp[1] = dWhp[1] ? dWhp[1] : dWhp[0]; a.Wop = dWop; a.KSp = enc.KS;
+      if ((rc = encoder_args(a, s))) return rc;
       HIPCHK(launch_lift_mlp<T>(a, s));
     } else {
       a.cx = dcx; a.eps = (T)cfg.rbf_eps; a.rbf_matlab = rbf_code();
@@ -933,8 +979,8 @@ struct Impl : kmpc_handle {
     a.out_kind = cfg.output_kind == KMPC_OUT_LIFT ? OUT_LIFT : OUT_CX;
     a.max_iter = cfg.qp_max_iter > 0 ? cfg.qp_max_iter : 8 * N + 40;
     a.P = dP; a.strideP = sP; a.K = dK; a.strideK = sK; a.Qb = dQ; a.strideQ = sQ; a.C = dC; a.strideC = sC;
-    a.Wterm = have_wterm ? (wterm_from_dare ? (T*)dWtB.get() : dWt.get()) : nullptr;
-    a.wterm_per_traj = (have_wterm && wterm_from_dare && wterm_per_traj) ? 1 : 0;
+    a.Wterm = wterm_ptr();
+    a.wterm_per_traj = wterm == Term::DarePerTraj ? 1 : 0;
     a.lam = (T)cfg.lambda; a.Qw = (T)cfg.Qw; a.Rw = (T)cfg.Rw; a.lb = (T)cfg.lb; a.ub = (T)cfg.ub;
     a.du_mode = cfg.delta_u ? 1 : 0;
     a.cy0 = cfg.output_kind == KMPC_OUT_LIFT ? 0 : cfg.out_row0;
@@ -947,6 +993,10 @@ struct Impl : kmpc_handle {
     a.plant = -1;
     return a;
   }
+  // a step that also advances every trajectory's plant with its u_k (the roll-outs, kmpc_shared_solve_plant)
+  void plant_args(StepArgs<T>& a, const StepCtx& ctx) {
+    if (ctx.plant >= 0) { a.plant = ctx.plant; a.plant_switched = ctx.switched; a.plant_h = (T)ctx.h; a.X_rw = (T*)ctx.X_rw; }
+  }
 
   int rls_update(const void* psi, const void* u, const void* psin, const void* xn, int Bc, hipStream_t s) override {
     if (Bc != B) FAIL(-3, "kmpc_rls_update: B must equal the handle's batch (the state is per trajectory)");
@@ -954,12 +1004,12 @@ struct Impl : kmpc_handle {
     { int rc = ensure_dense(s, true); if (rc) return rc; }
     StepArgs<T> a = base_args(Bc);
     a.phases = PH_RLS;
-    a.first_update = rls_fresh ? 1 : 0;
+    a.first_update = prog.rls_fresh ? 1 : 0;
     a.psi_prev = (const T*)psi; a.pp_sl = Bc; a.pp_sb = 1;
     a.psi_now = (const T*)psin; a.pn_sl = Bc; a.pn_sb = 1;
     a.u_prev = (const T*)u; a.x_now = (const T*)xn;
     HIPCHK(launch_step<T>(a, threads, s));
-    rls_fresh = false;
+    prog.rls_fresh = false;
     return 0;
   }
 
@@ -984,7 +1034,6 @@ struct Impl : kmpc_handle {
   }
 
   // kmpc_mpc_solve: the solve wrapper with the model as an argument; scratch model blocks, H, f, c are the handle's
-  DevBuf<T> dMsK, dMsC, dMsH, dMsf, dMsc, dMsW;
   int mpc_solve(const void* A, const void* Bv, const void* C, int shared, const void* psi, const void* ref, int rpt,
                 double lb_, double ub_, double Qw_, double Rw_, const double* PN, void* U, void* U0, void* fun,
                 int32_t* st, int32_t* it, int Bc, hipStream_t s) override {
@@ -1002,9 +1051,7 @@ struct Impl : kmpc_handle {
     HIPCHK(launch_import_model<T>((const T*)A, (const T*)Bv, (const T*)C, shared, n, L, B, dMsK, sK,
                                   cfg.output_kind == KMPC_OUT_CX ? dMsC : nullptr, sC, s));
     if (PN) {
-      std::vector<T> w((size_t)q * q);
-      for (int r = 0; r < q; ++r)
-        for (int c2 = 0; c2 < q; ++c2) w[(size_t)r * q + c2] = (T)(PN[(size_t)r * q + c2] - (r == c2 ? Qw_ : 0.0));
+      const std::vector<T> w = block_from_pn(PN, Qw_);
       HIPCHK(hipMemcpyAsync(dMsW, w.data(), w.size() * sizeof(T), hipMemcpyHostToDevice, s));
       HIPCHK(hipStreamSynchronize(s));  // (the host vector goes out of scope)
     }
@@ -1014,11 +1061,9 @@ struct Impl : kmpc_handle {
     // the terminal block: P_N of this call, else the handle's (kmpc_set_terminal_weight / kmpc_terminal_from_dare), as
     // kmpc_condense and kmpc_step use it -- the same cost on every route through the handle
     if (PN) { a.Wterm = dMsW; a.wterm_per_traj = 0; }
-    else if (have_wterm && Qw_ != cfg.Qw) {
-      if (wterm_from_dare || hostPN.empty()) FAIL(-3, "kmpc_mpc_solve: the handle's terminal block was formed with the handle's Q; pass P_N with another Q");
-      std::vector<T> w((size_t)q * q);
-      for (int r = 0; r < q; ++r)
-        for (int c2 = 0; c2 < q; ++c2) w[(size_t)r * q + c2] = (T)(hostPN[(size_t)r * q + c2] - (r == c2 ? Qw_ : 0.0));
+    else if (wterm != Term::None && Qw_ != cfg.Qw) {
+      if (term_from_dare(wterm) || hostPN.empty()) FAIL(-3, "kmpc_mpc_solve: the handle's terminal block was formed with the handle's Q; pass P_N with another Q");
+      const std::vector<T> w = block_from_pn(hostPN.data(), Qw_);
       HIPCHK(hipMemcpyAsync(dMsW, w.data(), w.size() * sizeof(T), hipMemcpyHostToDevice, s));
       HIPCHK(hipStreamSynchronize(s));
       a.Wterm = dMsW; a.wterm_per_traj = 0;
@@ -1106,13 +1151,13 @@ struct Impl : kmpc_handle {
     int rc = prof_begin(s, &rec);
     if (rc) return rc;
     if ((rc = ensure_dense(s, true))) return rc;  // (first: on a float32 handle the ping-pong index follows the core's)
-    T* psi_now = dPsi[cur];
-    T* psi_prev = dPsi[cur ^ 1];
+    T* psi_now = dPsi[prog.cur];
+    T* psi_prev = dPsi[prog.cur ^ 1];
     if ((rc = lift_to((const T*)X, psi_now, 1, L, B, s))) return rc;
     if (rec && (rc = prof_mid(s))) return rc;
     StepArgs<T> a = base_args(B);
-    a.phases = PH_CONDENSE | PH_QP | ((have_prev && update_on) ? PH_RLS : 0);
-    a.first_update = rls_fresh ? 1 : 0;
+    a.phases = PH_CONDENSE | PH_QP | ((prog.have_prev && update_on) ? PH_RLS : 0);
+    a.first_update = prog.rls_fresh ? 1 : 0;
     a.psi_prev = psi_prev; a.pp_sl = 1; a.pp_sb = L;
     a.psi_now = psi_now; a.pn_sl = 1; a.pn_sb = L;
     a.u_prev = dUprev; a.x_now = (const T*)X;
@@ -1121,7 +1166,7 @@ struct Impl : kmpc_handle {
     a.x_warm = cfg.cold_start ? nullptr : dWarm;
     a.qp_carry = dQpCarry; a.qp_carry_set = dQpCarrySet;
     a.accumulate = ctx.accumulate ? 1 : 0;
-    if (ctx.plant >= 0) { a.plant = ctx.plant; a.plant_switched = ctx.switched; a.plant_h = (T)ctx.h; a.X_rw = (T*)ctx.X_rw; }
+    plant_args(a, ctx);
     if (term_every > 0) {
       // per-step terminal refresh on the per-step route: the RLS update as a launch of its own, the Riccati iteration on the updated
       // models (dare_kernel, every term_every-th step), then condensed QP and solve with the refreshed blocks
@@ -1138,18 +1183,13 @@ struct Impl : kmpc_handle {
     }
     HIPCHK(launch_step<T>(a, threads, s));
     if (rec && (rc = prof_end(s, 1))) return rc;
-    if (have_prev && update_on) rls_fresh = false;
-    have_prev = true;
-    cur ^= 1;
+    prog.advance(1, update_on);
     return 0;
   }
 
+  int set_online_update(int on) override { update_on = on != 0; if (core) core->update_on = update_on; return 0; }
   // the input that was actually applied at the last step, when it is not the one kmpc_step returned (actuator limits, a
   // logged trajectory that is being followed): the next RLS update regresses on it (z = [psi; u], duffing.py:900)
-  // the loop WITHOUT the online update (duffing.py:738-805, vanderpol.py:645-722): kmpc_step / kmpc_rollout skip the RLS phase and
-  // solve with the model as it is; the lift / input history keeps running, so that switching the update back on continues
-  bool update_on = true;
-  int set_online_update(int on) override { update_on = on != 0; if (core) core->update_on = update_on; return 0; }
   int set_applied_input(const void* U, int Bc, hipStream_t s) override {
     if (!U || Bc != B) FAIL(-3, "kmpc_set_applied_input: U must hold one input per trajectory of the handle");
     if (core) { const int rc = ensure_dense(s, true); if (rc) return rc; }  // (u_{k-1} is part of what the core owns during roll-outs)
@@ -1167,9 +1207,6 @@ struct Impl : kmpc_handle {
   }
 
   // ---- fused roll-out (one launch for all the steps; rollout_kernel in step_kernel.hip) ----------------
-  DevBuf<T> dWhp[2], dWop;  // hidden / output weights as MFMA A-fragments
-  bool packed_ok = false;
-  int64_t prof_steps = 0;   // profiling: control steps covered by the recorded events
   int pack_encoder(hipStream_t s) {
     if (packed_ok) return 0;
     const int KS = enc.KS;
@@ -1225,10 +1262,9 @@ struct Impl : kmpc_handle {
       if (core) {
         if ((rc = ensure_image(s))) return rc;
         core->prof = prof;
-        rc = core->rollout_fused(ctx, plant, X, ref, rpt, steps, step0, switch_step, hs, Ulog, Xlog, st, it, s, U0out, Useqout, true);
-        if (rc) { err = core->err; return rc; }
-        have_prev = core->have_prev; rls_fresh = core->rls_fresh; cur = core->cur;
-        return 0;
+        rc = on_core([&](Impl<double>& c) { return c.rollout_fused(ctx, plant, X, ref, rpt, steps, step0, switch_step, hs, Ulog, Xlog, st, it, s, U0out, Useqout, true); });
+        if (!rc) prog = core->prog;
+        return rc;
       }
     }
     RolloutArgs<T> r{};
@@ -1249,9 +1285,9 @@ struct Impl : kmpc_handle {
       r.lift_rbf = 1;
       r.cx = dcx; r.eps = (T)cfg.rbf_eps; r.rbf_matlab = rbf_code();
     }
-    r.psi[0] = dPsi[0]; r.psi[1] = dPsi[1]; r.cur = cur;
+    r.psi[0] = dPsi[0]; r.psi[1] = dPsi[1]; r.cur = prog.cur;
     r.steps = steps; r.step0 = step0; r.switch_step = switch_step;
-    r.have_prev = have_prev ? 1 : 0; r.rls_fresh = rls_fresh ? 1 : 0;
+    r.have_prev = prog.have_prev ? 1 : 0; r.rls_fresh = prog.rls_fresh ? 1 : 0;
     r.no_update = update_on ? 0 : 1;
     r.U_log = (T*)Ulog; r.X_log = (T*)Xlog;
     r.io_f32 = io32 ? 1 : 0;
@@ -1306,14 +1342,10 @@ struct Impl : kmpc_handle {
       place_stream = s;
     }
     if (term_every > 0) term_count += steps;
-    // the host-side flags follow the kernel's own bookkeeping
-    if (update_on && (steps >= 2 || (steps == 1 && have_prev))) rls_fresh = false;
-    have_prev = true;
-    cur ^= (steps & 1);
+    prog.advance(steps, update_on);  // (the host side follows the kernel's own bookkeeping)
     return 0;
   }
 
-  DevBuf<T> dU0;  // rollout scratch [B]
   int rollout(int plant, void* X, const void* ref, int rpt, int steps, int step0, int switch_step, double hs,
               void* Ulog, void* Xlog, int32_t* st, int32_t* it, hipStream_t s) override {
     return rollout_impl(StepCtx{}, plant, X, ref, rpt, steps, step0, switch_step, hs, Ulog, Xlog, st, it, s);
@@ -1343,15 +1375,11 @@ struct Impl : kmpc_handle {
     if (steps > 0) last_rollout_variant = last_rollout_resident = last_rollout_lds = 0;
     if (steps == 0 && fused) {
       // a call without steps brings the handle into the form the fused roll-out works on (the wave image of a state that was
-      // set, restored or stepped through the dense blocks): set-up that the next kmpc_rollout would otherwise pay
-      if constexpr (sizeof(T) == 8) {
-        if (use_img) return ensure_image(s);
-      } else if (core) {
-        int rc = ensure_image(s);
-        if (!rc && core->use_img && (rc = core->ensure_image(s))) err = core->err;
-        return rc;
-      }
-      return 0;
+      // set, restored or stepped through the dense blocks): set-up that the next kmpc_rollout would otherwise pay -- a float32 handle's
+      // core, then the core's own image
+      int rc = ensure_image(s);
+      if (!rc) rc = on_core([&](Impl<double>& c) { return c.ensure_image(s); });
+      return rc;
     }
     for (int i = 0; i < steps; ++i) {
       const int gi = step0 + i;
@@ -1367,28 +1395,6 @@ struct Impl : kmpc_handle {
   }
 
   // ---- shared-model mode -----------------------------------------------------------------------------
-  DevBuf<double> dGram, dPartial;  // (dGram set: the handle has its shared-model blocks, all seven -- shared_alloc)
-  DevBuf<T> dKs, dCs, dHs, dFs, df0s, dTs;
-  DevBuf<double> dFastPack;      // F, T0, H of the shared model as shared_fast_kernel's operand fragments (SharedModel2Args::pack)
-  bool fast_pack_valid = false;  // ... written by the last model launch
-  DevBuf<int32_t> dNeed;  // [B] flags of shared_fast_kernel
-  DevBuf<int32_t> dWork;  // [B] solver work of every trajectory in the last fused launch (RolloutArgs::work)
-  DevBuf<int32_t> dPerm;  // [B] slot -> trajectory for the next fused launch (RolloutArgs::perm); valid after a launch that wrote dWork
-  bool place_valid = false;
-  hipEvent_t evPlace = nullptr;      // recorded behind the launch (and the rank pass) that wrote dWork / dPerm
-  hipStream_t place_stream = nullptr;
-  DevBuf<int32_t> dQpList;  // two alternating counters, then the list of the trajectories shared_fast_kernel left to the solve-only kernel
-  int qp_list_parity = 0;
-  DevBuf<T> dWt;  // PN - Qw I (terminal block of Q_bar)
-  std::vector<double> hostPN;  // P_N as given to kmpc_set_terminal_weight
-  bool have_wterm = false;
-  // kmpc_terminal_from_dare: Riccati workspace and the block(s) it produced ([1] or [B][q*q], PN - Qw I)
-  DevBuf<double> dDareP, dWtB;
-  DevBuf<int32_t> dDareIt;
-  int dare_cap = 0;  // models the three hold room for (dare_buffers alone changes it)
-  bool wterm_from_dare = false, wterm_per_traj = false;
-  bool shared_has_samples = false;
-  static constexpr int GRAM_BLOCKS = 256;  // partial blocks of the Gram kernels (512 measured slower: lift + Gram 21.8 vs 17.2 us, reduce 7.6 vs 4.8 us)
   int64_t gram_elems() const override { return (int64_t)(p + L + n) * p; }
   // the seven blocks of the shared-model mode, made and filled in locals and handed to the handle together: a call that fails leaves the
   // handle without any of them, and the next one starts over
@@ -1436,9 +1442,10 @@ struct Impl : kmpc_handle {
     int rc = shared_route_check("kmpc_shared_local_gram");
     if (rc) return rc;
     if ((rc = shared_alloc())) return rc;
-    if (core && (rc = ensure_dense(s, true))) return rc;  // (psi, u_{k-1} and the ping-pong index are this side's from here on)
-    T* psi_now = dPsi[cur];
-    T* psi_prev = dPsi[cur ^ 1];
+    // (only `if (core)`: psi, u_{k-1} and the ping-pong index are this side's from here on; the wave image of a float64 handle holds none of them)
+    if (core && (rc = ensure_dense(s, true))) return rc;
+    T* psi_now = dPsi[prog.cur];
+    T* psi_prev = dPsi[prog.cur ^ 1];
     GramArgs<T> g{};
     g.B = B; g.n = n; g.L = L; g.max_blocks = GRAM_BLOCKS;
     g.psi_prev = psi_prev; g.pp_sl = 1; g.pp_sb = L;
@@ -1447,15 +1454,12 @@ struct Impl : kmpc_handle {
     if constexpr (sizeof(T) == 8) {
       // float64 MLP lift: the lift and the Gram sums of the transitions in ONE launch (lift_coop_kernel<.., GRAM>), then the reduce
       const bool two = dbg_env("KMPC_SHARED_LIFT_GRAM_2") != nullptr;  // measurement / test aid (read per call): the two round-3 launches
-      if (have_prev && !two && cfg.lift_kind == KMPC_LIFT_MLP) {
+      if (prog.have_prev && !two && cfg.lift_kind == KMPC_LIFT_MLP) {
         if ((rc = check_lift_ready())) return rc;
         LiftArgs<T> a{};
         a.B = B; a.n = n; a.L = L; a.hidden = enc.hid; a.nlayers = cfg.layers;
         a.X = (const T*)X; a.Psi = psi_now; a.ps_l = 1; a.ps_b = L;
-        a.W1 = dW1; a.b1 = db1; a.Wh[0] = dWh[0]; a.Wh[1] = dWh[1]; a.bh[0] = dbh[0]; a.bh[1] = dbh[1];
-        a.Wo = dWo; a.bo = dbo; a.Hp = enc.Hp; a.Lp = enc.Lp;
-        if ((rc = pack_encoder(s))) return rc;
-        a.Whp[0] = dWhp[0]; a.Whp[1] = dWhp[1] ? dWhp[1] : dWhp[0]; a.Wop = dWop; a.KSp = enc.KS;
+        if ((rc = encoder_args(a, s))) return rc;
         if (lift_gram_available(a)) {
           int nb = 0;
           HIPCHK(launch_lift_gram(a, g, &nb, s));
@@ -1466,7 +1470,7 @@ struct Impl : kmpc_handle {
     }
     rc = lift_to((const T*)X, psi_now, 1, L, B, s);
     if (rc) return rc;
-    if (!have_prev) {
+    if (!prog.have_prev) {
       HIPCHK(hipMemsetAsync(delta, 0, sizeof(double) * (size_t)gram_elems(), s));
       return 0;
     }
@@ -1481,7 +1485,6 @@ struct Impl : kmpc_handle {
     return shared_solve_impl(StepCtx{false, plant, switched ? 1 : 0, hstep, X, nullptr}, delta, ref, U0, Useq, st, it, s);
   }
   // kmpc_shared_rollout: the stages of the shared-model step, `steps` times, on one stream, the collective between them
-  DevBuf<double> dDelta;  // this rank's Gram sums of a step (all-reduced in place)
   int shared_rollout(int plant, void* X, const void* ref, int steps, int step0, int switch_step, double hstep, void* comm, void* Ulog,
                      void* Xlog, void* U0out, void* Useq, int32_t* st, int32_t* it, hipStream_t s) override {
     if (!X || !ref || steps < 0) FAIL(-3, "kmpc_shared_rollout: bad arguments");
@@ -1503,7 +1506,7 @@ struct Impl : kmpc_handle {
     for (int i = 0; i < steps; ++i) {
       const int gi = step0 + i;
       if ((rc = shared_local_gram(X, dDelta, s))) return rc;
-      if (ar && have_prev) {  // (before the first transition every rank's block is zero: nothing to sum)
+      if (ar && prog.have_prev) {  // (before the first transition every rank's block is zero: nothing to sum)
         const ncclResult_t nr = ar(dDelta, dDelta, (size_t)gram_elems(), ncclDouble, ncclSum, (ncclComm_t)comm, s);
         if (nr != ncclSuccess) FAIL(-(2000 + (int)nr), "kmpc_shared_rollout: ncclAllReduce failed");
       }
@@ -1521,17 +1524,17 @@ struct Impl : kmpc_handle {
   }
   int shared_solve_impl(const StepCtx& ctx, const double* delta, const void* ref, void* U0, void* Useq, int32_t* st, int32_t* it, hipStream_t s) {
     if (!delta || !ref || !U0) FAIL(-3, "kmpc_shared_solve: null pointer");
-    if (have_wterm && wterm_from_dare && wterm_per_traj)
+    if (wterm == Term::DarePerTraj)
       FAIL(-3, "kmpc_shared_solve: per-trajectory terminal blocks do not apply to the shared model (kmpc_terminal_from_dare with per_trajectory = 0)");
     int rc = shared_route_check("kmpc_shared_solve");
     if (rc) return rc;
     if ((rc = shared_alloc())) return rc;
-    if (core && (rc = ensure_dense(s, true))) return rc;
-    const T* wt = !have_wterm ? nullptr : (wterm_from_dare ? (const T*)dWtB.get() : dWt.get());
+    if (core && (rc = ensure_dense(s, true))) return rc;  // (only `if (core)`, as in shared_local_gram: u_{k-1} and the warm start are written here)
+    const T* wt = wterm_ptr();
     const int okind = cfg.output_kind == KMPC_OUT_LIFT ? OUT_LIFT : OUT_CX;
     const int cy0 = cfg.output_kind == KMPC_OUT_LIFT ? 0 : cfg.out_row0;
     const bool one_launch = shared_one_launch();
-    if (have_prev && !one_launch) HIPCHK(launch_axpby(dGram, delta, cfg.lambda, (int)gram_elems(), s));
+    if (prog.have_prev && !one_launch) HIPCHK(launch_axpby(dGram, delta, cfg.lambda, (int)gram_elems(), s));
     if (one_launch) {
       // model solve + condensed QP + the tableau the box QPs start from, one launch (shared_model_kernel)
       HIPCHK(dTs.ensure((size_t)N * N));
@@ -1540,8 +1543,8 @@ struct Impl : kmpc_handle {
       if constexpr (sizeof(T) == 8) {
         if (!old_kernel && shared_model2_available(L, n, q, N, cfg.delta_u ? 1 : 0)) {
           SharedModel2Args m{};
-          m.gram = dGram; m.delta = have_prev ? delta : nullptr; m.forget = cfg.lambda; m.ref = (const double*)ref;
-          m.Lm = L; m.n = n; m.q = q; m.N = N; m.dP = 1.0 / cfg.P0; m.dQ = 1.0 / cfg.barQ0; m.have_samples = have_prev ? 1 : 0;
+          m.gram = dGram; m.delta = prog.have_prev ? delta : nullptr; m.forget = cfg.lambda; m.ref = (const double*)ref;
+          m.Lm = L; m.n = n; m.q = q; m.N = N; m.dP = 1.0 / cfg.P0; m.dQ = 1.0 / cfg.barQ0; m.have_samples = prog.have_prev ? 1 : 0;
           m.Qw = cfg.Qw; m.Rw = cfg.Rw;
           m.Kio = (double*)dKs; m.Cio = (double*)dCs; m.Hout = (double*)dHs; m.Fout = (double*)dFs; m.f0out = (double*)df0s; m.Tout = (double*)dTs;
           m.Wt = (const double*)wt; m.du_mode = cfg.delta_u ? 1 : 0; m.cy0 = cy0;
@@ -1562,12 +1565,12 @@ struct Impl : kmpc_handle {
       }
       if (!on16) {
         fast_pack_valid = false;
-        HIPCHK(launch_shared_model<T>(dGram, have_prev ? delta : nullptr, cfg.lambda, (const T*)ref, L, n, q, N, 1.0 / cfg.P0, 1.0 / cfg.barQ0, 1, have_prev ? 1 : 0, cfg.Qw,
+        HIPCHK(launch_shared_model<T>(dGram, prog.have_prev ? delta : nullptr, cfg.lambda, (const T*)ref, L, n, q, N, 1.0 / cfg.P0, 1.0 / cfg.barQ0, 1, prog.have_prev ? 1 : 0, cfg.Qw,
                                       cfg.Rw, dKs, dCs, dHs, dFs, df0s, dTs, wt, cfg.delta_u ? 1 : 0, cy0, s));
       }
-      if (have_prev) shared_has_samples = true;
+      if (prog.have_prev) shared_has_samples = true;
     } else {
-      if (have_prev) {
+      if (prog.have_prev) {
         HIPCHK(launch_shared_solve<T>(dGram, L, n, 1.0 / cfg.P0, 1.0 / cfg.barQ0,
                                       cfg.output_kind == KMPC_OUT_CX ? 1 : 0, dKs, dCs, s, nullptr, nullptr, 1));
         shared_has_samples = true;
@@ -1580,12 +1583,11 @@ struct Impl : kmpc_handle {
     a.H_in = dHs; a.h_shared = 1; a.F_in = dFs; a.f0_in = df0s;
     a.T_in = one_launch ? dTs : nullptr;
     a.fast_pack = (one_launch && fast_pack_valid) ? dFastPack : nullptr;
-    a.psi_now = dPsi[cur]; a.pn_sl = 1; a.pn_sb = L;
+    a.psi_now = dPsi[prog.cur]; a.pn_sl = 1; a.pn_sb = L;
     a.U0 = (T*)U0; a.Useq = (T*)Useq; a.u_store = dUprev; a.status = st; a.iters = it;
     a.x_warm = cfg.cold_start ? nullptr : dWarm;
     a.accumulate = ctx.accumulate ? 1 : 0;  // (kmpc_shared_rollout: worst status / total Newton solves over the steps)
-    // (kmpc_shared_solve_plant: the solve also advances every trajectory's plant with its u_k, as the roll-outs do)
-    if (ctx.plant >= 0) { a.plant = ctx.plant; a.plant_switched = ctx.switched; a.plant_h = (T)ctx.h; a.X_rw = (T*)ctx.X_rw; }
+    plant_args(a, ctx);  // (kmpc_shared_solve_plant: the solve also advances every trajectory's plant with its u_k, as the roll-outs do)
     bool rec;  // (profiling: the QP launch of the shared-model step)
     if ((rc = prof_begin(s, &rec)) || (rec && (rc = prof_mid(s)))) return rc;
     // the trajectories whose unconstrained minimiser lies inside the box are finished 16 per wave on the matrix cores
@@ -1609,8 +1611,9 @@ struct Impl : kmpc_handle {
     }
     HIPCHK(launch_step<T>(a, threads, s));
     if (rec && (rc = prof_end(s, 1))) return rc;
-    have_prev = true;
-    cur ^= 1;
+    // (not Progress::advance: the shared-model step runs no RLS update and never clears rls_fresh)
+    prog.have_prev = true;
+    prog.cur ^= 1;
     return 0;
   }
   int offline_fit(const void* X, const void* Y, const void* U, int M, double ridge, int init_rls, void* A, void* Bm,
@@ -1654,7 +1657,7 @@ struct Impl : kmpc_handle {
       if (e == hipSuccess) e = hipStreamSynchronize(s);
       if (e != hipSuccess) { err = std::string("kmpc_offline_fit: ") + hipGetErrorString(e); rc = -(int)(1000 + (int)e); }
     }
-    if (!rc && init_rls) rls_fresh = false;  // the first online update refines this model instead of restarting from K_A = 0
+    if (!rc && init_rls) prog.rls_fresh = false;  // the first online update refines this model instead of restarting from K_A = 0
     return rc;
   }
 
@@ -1667,15 +1670,14 @@ struct Impl : kmpc_handle {
   }
 
   // ---- state blob (the layout: the comment at BlobHeader, above Impl)
-  int32_t wterm_block_count(bool have, bool from_dare, bool per_traj) const { return !have ? 0 : ((from_dare && per_traj) ? B : 1); }
   // the header of a blob written now: which optional sections the handle has, and the flags that travel with the state
   BlobHeader blob_header() const {
     BlobHeader hd{};
     hd.magic = kBlobMagic; hd.version = 2; hd.dtype = cfg.dtype; hd.n = n; hd.L = L; hd.N = N; hd.B = B;
-    hd.have_prev = have_prev ? 1 : 0; hd.rls_fresh = rls_fresh ? 1 : 0;
+    hd.have_prev = prog.have_prev ? 1 : 0; hd.rls_fresh = prog.rls_fresh ? 1 : 0;
     hd.has_shared = dGram ? 1 : 0; hd.shared_has_samples = shared_has_samples ? 1 : 0;
-    hd.have_wterm = have_wterm ? 1 : 0; hd.wterm_from_dare = wterm_from_dare ? 1 : 0; hd.wterm_per_traj = wterm_per_traj ? 1 : 0;
-    hd.wterm_blocks = wterm_block_count(have_wterm, wterm_from_dare, wterm_per_traj);
+    term_to_flags(wterm, &hd.have_wterm, &hd.wterm_from_dare, &hd.wterm_per_traj);
+    hd.wterm_blocks = wterm_block_count(wterm);
     hd.P0 = cfg.P0; hd.barQ0 = cfg.barQ0;
     return hd;
   }
@@ -1686,7 +1688,7 @@ struct Impl : kmpc_handle {
     Sections t;
     t.add(dP, sizeof(T), (size_t)sP * B); t.add(dK, sizeof(T), (size_t)sK * B);
     t.add(dQ, sizeof(T), (size_t)sQ * B); t.add(dC, sizeof(T), (size_t)sC * B);
-    t.add(dPsi[cur ^ 1], sizeof(T), (size_t)L * B); t.add(dWarm, sizeof(T), (size_t)N * B, (size_t)N); t.add(dUprev, sizeof(T), (size_t)B);
+    t.add(dPsi[prog.cur ^ 1], sizeof(T), (size_t)L * B); t.add(dWarm, sizeof(T), (size_t)N * B, (size_t)N); t.add(dUprev, sizeof(T), (size_t)B);
     t.n_traj = t.n;
     if (hd.has_shared) { t.add(dGram, sizeof(double), (size_t)gram_elems()); t.add(dKs, sizeof(T), (size_t)L * p); t.add(dCs, sizeof(T), (size_t)n * L); }
     if (hd.have_wterm && hd.wterm_from_dare) t.add(dWtB, sizeof(double), (size_t)hd.wterm_blocks * q * q);
@@ -1699,7 +1701,7 @@ struct Impl : kmpc_handle {
     { int rc = sync_own(); if (rc) return rc; }  // (a roll-out on a non-blocking stream may still be writing the wave image)
     { int rc = ensure_dense(nullptr, false); if (rc) return rc; }
     { int rc = forget_tableaux(nullptr); if (rc) return rc; }  // (a checkpoint is a synchronisation point: exporter and importer continue alike)
-    if (core) img_valid = false;  // (... a float32 handle from its float32 blocks, as the importer will, not from its core's unrounded state)
+    if (core) home.drop_fast();  // (... a float32 handle from its float32 blocks, as the importer will, not from its core's unrounded state)
     HIPCHK(hipStreamSynchronize(nullptr));
     const BlobHeader hd = blob_header();
     const Sections t = sections(hd);
@@ -1725,45 +1727,40 @@ struct Impl : kmpc_handle {
     if (!flag01(hd.have_prev) || !flag01(hd.rls_fresh) || !flag01(hd.has_shared) || !flag01(hd.shared_has_samples) || !flag01(hd.have_wterm) ||
         !flag01(hd.wterm_from_dare) || !flag01(hd.wterm_per_traj))
       FAIL(-3, "kmpc_state_import: inconsistent header (flags)");
-    if (hd.wterm_blocks != wterm_block_count(hd.have_wterm, hd.wterm_from_dare, hd.wterm_per_traj) ||
-        (!hd.have_wterm && (hd.wterm_from_dare || hd.wterm_per_traj)) || (hd.wterm_per_traj && !hd.wterm_from_dare))
-      FAIL(-3, "kmpc_state_import: inconsistent header (terminal blocks)");
-    if (hd.wterm_from_dare && sizeof(T) != 8) FAIL(-3, "kmpc_state_import: Riccati terminal blocks need a float64 handle");
+    bool term_ok;
+    const Term blob_term = term_from_flags(hd.have_wterm, hd.wterm_from_dare, hd.wterm_per_traj, &term_ok);
+    if (!term_ok || hd.wterm_blocks != wterm_block_count(blob_term)) FAIL(-3, "kmpc_state_import: inconsistent header (terminal blocks)");
+    if (term_from_dare(blob_term) && sizeof(T) != 8) FAIL(-3, "kmpc_state_import: Riccati terminal blocks need a float64 handle");
     if (bytes < blob_bytes(sections(hd))) FAIL(-3, "kmpc_state_import: buffer too small");
     { int rc = sync_own(); if (rc) return rc; }
-    dense_valid = true; img_valid = false;  // (the blob overwrites every dense block)
+    home.dense_overwritten();  // (the blob overwrites every dense block)
     { int rc = forget_tableaux(nullptr); if (rc) return rc; }
     if (hd.has_shared) { int rc = shared_alloc(); if (rc) return rc; }
-    if (hd.have_wterm) {
-      if (hd.wterm_from_dare) { int rc = dare_buffers(hd.wterm_blocks); if (rc) return rc; }
-      else HIPCHK(dWt.ensure((size_t)q * q));
-    }
+    if (term_from_dare(blob_term)) { int rc = dare_buffers(hd.wterm_blocks); if (rc) return rc; }
+    else if (blob_term == Term::Given) HIPCHK(dWt.ensure((size_t)q * q));
     const Sections t = sections(hd);  // (now that every section of the blob has its buffer)
     for (int i = 0; i < t.n; ++i) {
       HIPCHK(hipMemcpy(t.s[i].ptr, o, t.s[i].bytes(), hipMemcpyDefault));
       o += t.s[i].bytes();
     }
-    have_prev = hd.have_prev != 0;
-    rls_fresh = hd.rls_fresh != 0;
+    prog.have_prev = hd.have_prev != 0;
+    prog.rls_fresh = hd.rls_fresh != 0;
     if (hd.has_shared) shared_has_samples = hd.shared_has_samples != 0;
     else if (dGram) {  // the blob comes from a handle that never ran a shared-model step
       HIPCHK(hipMemset(dGram, 0, sizeof(double) * (size_t)gram_elems()));
       shared_has_samples = false;
     }
-    have_wterm = hd.have_wterm != 0; wterm_from_dare = hd.wterm_from_dare != 0; wterm_per_traj = hd.wterm_per_traj != 0;
+    wterm = blob_term;
     cfg.P0 = hd.P0; cfg.barQ0 = hd.barQ0;
     if constexpr (sizeof(T) == 8) {
       // terminal refresh armed: its launches read one block per trajectory (dWtB[B]) whatever the blob held.  A blob with one block
       // for the batch (or none) gives that block (or Qw I) to every trajectory until its next refresh -- the copy above filled
       // trajectory 0 alone and left the other B - 1 what they were before the import.
-      if (term_every > 0 && !(have_wterm && wterm_from_dare && wterm_per_traj)) {
+      if (term_every > 0 && wterm != Term::DarePerTraj) {
         std::vector<double> w0((size_t)q * q, 0.0);
-        if (have_wterm) HIPCHK(hipMemcpy(w0.data(), wterm_from_dare ? (const void*)dWtB : (const void*)dWt, sizeof(double) * w0.size(), hipMemcpyDeviceToHost));
-        { int rc = dare_buffers(B); if (rc) return rc; }
-        std::vector<double> wb((size_t)B * q * q);
-        for (int b = 0; b < B; ++b) std::copy(w0.begin(), w0.end(), wb.begin() + (size_t)b * q * q);
-        HIPCHK(hipMemcpy(dWtB, wb.data(), sizeof(double) * wb.size(), hipMemcpyHostToDevice));
-        have_wterm = true; wterm_from_dare = true; wterm_per_traj = true;
+        if (wterm != Term::None) HIPCHK(hipMemcpy(w0.data(), wterm_ptr(), sizeof(double) * w0.size(), hipMemcpyDeviceToHost));
+        { int rc = spread_block(w0); if (rc) return rc; }
+        wterm = Term::DarePerTraj;
       }
     }
     // the host copy of a given P_N (kmpc_mpc_solve with another Q re-forms the block from it) and -- float32 handle with a float64
@@ -1771,24 +1768,20 @@ struct Impl : kmpc_handle {
     // checkpoint loaded into a fresh handle would otherwise run its fused roll-outs WITHOUT the terminal block, and one without a block
     // loaded over a handle that had one would keep using it
     hostPN.clear();
-    if (have_wterm && !wterm_from_dare) {
+    if (wterm == Term::Given) {
       std::vector<T> w((size_t)q * q);
       HIPCHK(hipMemcpy(w.data(), dWt, sizeof(T) * w.size(), hipMemcpyDeviceToHost));
-      hostPN.resize(w.size());
-      for (int r = 0; r < q; ++r)
-        for (int c2 = 0; c2 < q; ++c2) hostPN[(size_t)r * q + c2] = (double)w[(size_t)r * q + c2] + (r == c2 ? cfg.Qw : 0.0);
+      hostPN = pn_from_block(w, cfg.Qw);
       return core_weight(&w);
     }
     return core_weight(nullptr);
   }
 
   // ---- packed rows: trajectories in and out of the handle on the device (the row format: the comment behind BlobHeader)
-  DevBuf<int32_t> dRowChk;  // [B] marks of the duplicate check, then the status word of state_rows_check_kernel
-  DevBuf<T> dRowStage;      // kmpc_state_transfer into this handle: the packed rows between gather and scatter, grown on demand
   // a trajectory of this handle has state of its own that a row carries whole
   bool rows_supported(const char* who) const {
     if (dGram) { err = std::string(who) + ": the handle has its shared-model blocks -- the model is pooled over the batch, a trajectory has no state of its own"; return false; }
-    if ((have_wterm && wterm_from_dare && wterm_per_traj) || term_every > 0) {
+    if (wterm == Term::DarePerTraj || term_every > 0) {
       err = std::string(who) + ": per-trajectory terminal blocks (kmpc_terminal_from_dare per trajectory, kmpc_set_terminal_refresh) are no part of a packed row";
       return false;
     }
@@ -1831,8 +1824,8 @@ struct Impl : kmpc_handle {
     // a synchronisation point for the source, as kmpc_state_export is
     { int rc = ensure_dense(s, false); if (rc) return rc; }
     { int rc = forget_tableaux(s); if (rc) return rc; }
-    if (core) img_valid = false;  // (a float32 handle continues from its rounded float32 blocks, as the receiver of the rows will)
-    HIPCHK(launch_state_rows_gather<T>(pl, idx, count, B, (T*)rows, have_prev ? 1 : 0, rls_fresh ? 1 : 0, s));
+    if (core) home.drop_fast();  // (a float32 handle continues from its rounded float32 blocks, as the receiver of the rows will)
+    HIPCHK(launch_state_rows_gather<T>(pl, idx, count, B, (T*)rows, prog.have_prev ? 1 : 0, prog.rls_fresh ? 1 : 0, s));
     return 0;
   }
   int state_unpack(const int32_t* idx, int count, const void* rows, hipStream_t s) override {
@@ -1846,13 +1839,13 @@ struct Impl : kmpc_handle {
     // the flags belong to the handle: every row must carry its pair, except that a call which fills the whole handle brings its own
     const bool whole = !idx && count == B;
     int word = 0;
-    { int rc = rows_check("kmpc_state_unpack", pl, idx, count, idx != nullptr, rows, whole ? -1 : (have_prev ? 1 : 0), whole ? -1 : (rls_fresh ? 1 : 0), &word, s);
+    { int rc = rows_check("kmpc_state_unpack", pl, idx, count, idx != nullptr, rows, whole ? -1 : (prog.have_prev ? 1 : 0), whole ? -1 : (prog.rls_fresh ? 1 : 0), &word, s);
       if (rc) return rc; }
     { int rc = ensure_dense(s, true); if (rc) return rc; }  // (first: the trajectories the call leaves alone must be valid in the dense blocks)
     HIPCHK(launch_state_rows_scatter<T>(pl, idx, count, B, (const T*)rows, s));
-    dense_valid = true; img_valid = false;
+    home.dense_overwritten();
     { int rc = forget_tableaux(s); if (rc) return rc; }
-    if (whole) { have_prev = (word & ROWS_ROW0_HAVE_PREV) != 0; rls_fresh = (word & ROWS_ROW0_RLS_FRESH) != 0; }
+    if (whole) { prog.have_prev = (word & ROWS_ROW0_HAVE_PREV) != 0; prog.rls_fresh = (word & ROWS_ROW0_RLS_FRESH) != 0; }
     return 0;
   }
   int state_transfer(const int32_t* dst_idx, kmpc_handle* src_h, const int32_t* src_idx, int count, hipStream_t s) override {
@@ -1888,8 +1881,7 @@ struct Impl : kmpc_handle {
     int64_t core_steps = 0;
     if (core) {  // (the fused launches of a float32 handle are recorded by its core; both halves keep their totals on a non-resetting read)
       double c2[2] = {0, 0}; int64_t cc = 0;
-      const int rc = core->profile_read(c2, &cc, reset_);
-      if (rc) { err = core->err; return rc; }
+      if (const int rc = on_core([&](Impl<double>& c) { return c.profile_read(c2, &cc, reset_); })) return rc;
       a0 += c2[0]; a1 += c2[1]; core_steps = cc;
     }
     for (size_t i = 0; i + 2 < ev_used + 0 && i + 2 < ev.size(); i += 3) {

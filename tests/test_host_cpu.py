@@ -615,6 +615,26 @@ def test_device_buffer_type_on_a_failing_host_allocator(tmp_path):
     assert run.returncode == 0 and "devbuf ok" in run.stdout, (run.stdout, run.stderr[-3000:])
 
 
+def test_handle_state_types_against_the_flags_they_replaced(tmp_path):
+    """csrc/state_home.h (where a handle's state is valid, the estimator's progress, the kind of terminal block) on the CPU:
+    tests/state_home_check.cpp, built as a program of its own with AddressSanitizer and UBSan, holds the flag statements api.hip had
+    before as reference models.  Every sequence of up to six of the operations dense-read, dense-write, take-fast, dense-overwritten,
+    drop-fast and steps-0 prepare, with and without a fast form: StateHome asks for the same conversions at the same points as the two
+    booleans did, never without a fast form, and has no state for the pair (false, false) that the booleans could reach.
+    Progress::advance(steps, on) equals `steps` applications of the one-step rule (steps 0..5, update on and off, every start);
+    term_from_flags accepts exactly the four triples a handle can write and round-trips."""
+    rocm = os.path.dirname(os.path.dirname(os.path.realpath(_HIPCC)))
+    rocm_clang = os.path.join(rocm, "lib", "llvm", "bin", "clang++")
+    cxx = rocm_clang if os.access(rocm_clang, os.X_OK) else (shutil.which("clang++") or shutil.which("g++"))
+    exe = str(tmp_path / "state_home_check")
+    build = subprocess.run([cxx, "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                            "-I" + os.path.join(PKG, "csrc"), os.path.join(ROOT, "tests", "state_home_check.cpp"), "-o", exe],
+                           capture_output=True, text=True, timeout=300)
+    assert build.returncode == 0, build.stderr[-3000:]
+    run = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    assert run.returncode == 0 and "state_home ok" in run.stdout, (run.stdout, run.stderr[-3000:])
+
+
 def test_tools_scripts_compile():
     """VERDICT r5 hygiene: every script under tools/ is at least well-formed -- Python files byte-compile, shell scripts pass `bash -n` --
     and none of them refers to a compile-time experiment switch that no longer exists in the product headers."""
